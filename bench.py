@@ -2,6 +2,7 @@
 """Benchmark: forward+backward of the MI355X 3DGS rasterizer (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config 1m_1080p|100k_800|5m_1080p]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -14,6 +15,10 @@ the rank's Gaussian shard, all-to-all of the projected splats to the bands, band
 blend, asynchronous all-gather of the band images (overlaps B1), B1 on the band, all-to-all of
 the splats' 2D gradients back, B2 on the shard.  The whole image is rendered once per step for
 the job, so value = steps/s of the job ("scaling": "strong").  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, ms_per_step,
+counts); --dump-outputs DIR then also writes what the last timed step returned (image, radii,
+every gradient) as DIR/<name>.npy.  Everything below is measured only with --full.
 
 roofline: the dominant kernel's algorithmic HBM bytes (SURVEY §8d formulas) per
 launch / its mean launch time from HIP events recorded on the launch stream over the timed
@@ -206,6 +211,41 @@ class CppShard:
         return self._Band(self.st), g, self._Shard(radii)
 
 
+DUMP_BUDGET = 60_000_000  # bytes of .npy payload, all arrays together
+DUMP_SEED = 0
+
+
+def dump_outputs(path, whole, per_gaussian):
+    """Write the step's outputs as <path>/<name>.npy (float32; float64 arrays stay float64).
+    `whole` arrays are written in full.  `per_gaussian` arrays (first axis = Gaussian) are written
+    in full when everything fits DUMP_BUDGET; otherwise the same seeded, sorted sample of rows
+    of each, with the rows' indices in sample_index.npy (float64)."""
+    os.makedirs(path, exist_ok=True)
+
+    def host(t):
+        a = t.detach().cpu().numpy()
+        return a if a.dtype == np.float64 else a.astype(np.float32)
+
+    used = 0
+    for name, t in whole.items():
+        a = host(t)
+        used += a.nbytes
+        np.save(os.path.join(path, name + ".npy"), a)
+    P = min((int(t.shape[0]) for t in per_gaussian.values()), default=0)
+    row_bytes = sum(t[0].numel() * (8 if t.dtype == torch.float64 else 4) for t in per_gaussian.values()) if P else 0
+    idx = None
+    if used + P * row_bytes > DUMP_BUDGET:
+        rows = max((DUMP_BUDGET - used) // (row_bytes + 8), 0)
+        if rows < 1:
+            raise SystemExit(f"--dump-outputs: the whole-image outputs alone take {used} bytes")
+        sel = np.sort(np.random.default_rng(DUMP_SEED).choice(P, size=int(rows), replace=False))
+        np.save(os.path.join(path, "sample_index.npy"), sel.astype(np.float64))
+        idx = torch.from_numpy(sel)
+    for name, t in per_gaussian.items():
+        t = t if idx is None else t[idx.to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), host(t))
+
+
 def _free_port() -> int:
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
@@ -277,8 +317,14 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="1m_1080p", choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-stage-events", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="render mode: also the per-stage event pass, the roofline figures and the CPU oracle's "
+                         "baseline / parity leg (a plain run only times the steps)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="render mode, --gpus 1: write the last timed step's outputs (image, radii, gradients) "
+                         "as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU oracle leg")
+    ap.add_argument("--no-stage-events", action="store_true", help="--full without the stage events / roofline")
     ap.add_argument("--views", type=int, default=8, help="--mode views: cameras per batch")
     ap.add_argument("--iters", type=int, default=30000, help="--mode loop: training iterations")
     ap.add_argument("--loop-gt", type=int, default=4_000_000, help="--mode loop: ground-truth Gaussians")
@@ -308,6 +354,9 @@ def main():
                     help="launcher plumbing only: start the --gpus ranks, join the process group, count the "
                          "ranks with one all-reduce, print that as a JSON line and exit (no GPU work)")
     args = ap.parse_args()
+    if args.dump_outputs and (args.gpus != 1 or args.mode != "render" or args.launch_check):
+        print("bench.py: --dump-outputs writes the render mode's outputs at --gpus 1", file=sys.stderr)
+        sys.exit(2)
     rc = launch_or_refuse(args)
     if rc is not None:
         sys.exit(rc)
@@ -389,7 +438,7 @@ def main():
     # event pair adds ~10 us of dispatch gap, so the timed loop below carries only the
     # dominant kernel's pair -- its live duration feeds `roofline`).
     stages, dom_stage = {}, None
-    if not args.no_stage_events:
+    if args.full and not args.no_stage_events:
         if dist:
             dist.barrier()
         native.profile_enable()
@@ -426,6 +475,8 @@ def main():
     value = args.steps / elapsed  # whole-image forward+backward iterations per second (job)
 
     K = st.num_rendered  # raises on a binning overflow
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"color": st.color}, {"radii": st.radii, **g})
     tiles = gx * gy
     M = (D + 1) ** 2
     if world > 1:  # K, pixels and tiles of the band; P and V of the shard
@@ -514,7 +565,7 @@ def main():
             "algorithmic_bytes_per_step": int(total_alg),
             "achieved_GBs": round(total_alg / (ms_per_step * 1e-3) / 1e9, 2),
             "frac_of_8TBs": round(total_alg / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import gsr_oracle  # cpu_baseline leg only: the checker / reported baseline
         cores = int(os.environ.get("OMP_NUM_THREADS", os.cpu_count() or 1))

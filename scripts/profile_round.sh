@@ -14,7 +14,7 @@ OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp
 export TMPDIR=/tmp
-BENCH="python3 $R/bench.py --config $CFG --steps 20 --warmup 5 --no-cpu-baseline"
+BENCH="python3 $R/bench.py --config $CFG --steps 20 --warmup 5 --full --no-cpu-baseline"
 PBENCH="python3 $R/bench.py --config $CFG --steps 3 --warmup 1 --no-cpu-baseline --no-stage-events"
 CAL=$R/scripts/ubench/fetch_calib
 step() {

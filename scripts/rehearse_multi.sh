@@ -11,6 +11,6 @@ for cfg in 1m_1080p 5m_1080p; do
 done
 for w in 2 4; do
   timeout -k 10 300 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $w --master-addr 127.0.0.1 \
-    --master-port $((29500 + w)) bench.py --gpus $w --steps 5 --warmup 2 --dist-backend gloo \
+    --master-port $((29500 + w)) bench.py --gpus $w --steps 5 --warmup 2 --full --dist-backend gloo \
     > $OUT/gloo_$w.log 2>&1 || exit $?
 done

@@ -67,6 +67,56 @@ def test_bad_gpu_count_refused():
     assert _run(["--gpus", "0", "--launch-check"]).returncode == 2
 
 
+def test_dump_outputs_is_the_single_gpu_render_runs(tmp_path):
+    for extra in (["--gpus", "2"], ["--mode", "train"]):
+        r = _run(extra + ["--dump-outputs", str(tmp_path / "o")])
+        assert r.returncode == 2 and "--dump-outputs" in r.stderr, (extra, r.stderr[-2000:])
+    assert not (tmp_path / "o").exists()
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """bench.dump_outputs: float32 .npy files; everything in full under the budget; past it the
+    whole-image arrays in full and one seeded, sorted sample of rows shared by every per-Gaussian
+    array, the same from call to call, within the budget."""
+    import numpy as np
+    import torch
+
+    import bench
+    rng = np.random.default_rng(5)
+    P = 1000
+    color = torch.tensor(rng.standard_normal((3, 8, 10)), dtype=torch.float32)
+    per = {"radii": torch.arange(P, dtype=torch.int32),
+           "sh_rest": torch.tensor(rng.standard_normal((P, 15, 3)), dtype=torch.float32),
+           "means3D": torch.tensor(rng.standard_normal((P, 3)), dtype=torch.float32)}
+
+    def load(d):
+        return {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+
+    bench.dump_outputs(str(tmp_path / "all"), {"color": color}, per)
+    got = load(tmp_path / "all")
+    assert sorted(got) == ["color", "means3D", "radii", "sh_rest"]
+    assert all(a.dtype == np.float32 for a in got.values())
+    np.testing.assert_array_equal(got["color"], color.numpy())
+    np.testing.assert_array_equal(got["radii"], np.arange(P, dtype=np.float32))
+    np.testing.assert_array_equal(got["sh_rest"], per["sh_rest"].numpy())
+
+    budget = 20_000
+    monkeypatch.setattr(bench, "DUMP_BUDGET", budget)
+    bench.dump_outputs(str(tmp_path / "a"), {"color": color}, per)
+    bench.dump_outputs(str(tmp_path / "b"), {"color": color}, per)
+    a, b = load(tmp_path / "a"), load(tmp_path / "b")
+    assert sorted(a) == ["color", "means3D", "radii", "sample_index", "sh_rest"]
+    for k in a:
+        np.testing.assert_array_equal(a[k], b[k])
+    assert sum(v.nbytes for v in a.values()) <= budget
+    idx = a["sample_index"].astype(np.int64)
+    assert 1 < len(idx) < P and np.all(np.diff(idx) > 0) and a["sample_index"].dtype == np.float64
+    np.testing.assert_array_equal(a["color"], color.numpy())
+    np.testing.assert_array_equal(a["radii"], idx.astype(np.float32))  # radii[i] == i: the rows named
+    np.testing.assert_array_equal(a["sh_rest"], per["sh_rest"].numpy()[idx])
+    np.testing.assert_array_equal(a["means3D"], per["means3D"].numpy()[idx])
+
+
 def test_store_exchange_counts_the_ranks_that_joined(tmp_path):
     """bench.py --dist-backend gloo --dist-impl cpp runs the C++ gsr::ShardStep over
     ext.store_exchange on the launcher's c10d store; its comm_world, which the
