@@ -215,6 +215,7 @@ struct Views {
     uint2* ranges;
     uint32_t *counters, *K_dev, *ovf, *ovf2, *done, *term;
     float *final_T, *accum;
+    float *accum_z, *ckz;  // aux buffers only (GSR_LAYOUT_AUX): depth sum plane, depth checkpoints
     float4* ck;  // the checkpoint pool (binning buffer)
     size_t ck_bytes;
     uint32_t *kA, *vA, *kB, *vB, *hist;
@@ -246,7 +247,9 @@ int check_layout(const gsr_camera* cam, int ty0, int ty1, const gsr_buffers* b) 
                     b->layout, GSR_ABI_VERSION);
     const int gx = div_up(cam->width, kTile), gy = div_up(cam->height, kTile);
     const uint32_t want = expected_layout(b->n_local, gx, gy, b->capacity, (ty1 - ty0) * gx);
-    if (b->layout != want)
+    // the aux bits say which forward sized the buffers; aux buffers hold the plain arrays at the
+    // plain offsets, so every plain use accepts them (gsr_backward_aux asks for the bits itself)
+    if ((b->layout & ~(kBufAux | kBufInvDepth)) != want || (b->layout & (kBufAux | kBufInvDepth)) == kBufInvDepth)
         return fail(GSR_ERR_LAYOUT,
                     "gsr_buffers.layout = 0x%08x disagrees with the buffers (0x%08x for %d entries, capacity %d, "
                     "tile rows [%d, %d) of %d x %d)",
@@ -257,7 +260,8 @@ int check_layout(const gsr_camera* cam, int ty0, int ty1, const gsr_buffers* b) 
 Views views(const gsr_camera* cam, long long n, const gsr_buffers* b) {
     Views v{};
     const GeomLayout gl(n);
-    const ImgLayout il(cam->width, cam->height);
+    const bool aux = (b->layout & kBufAux) != 0;
+    const ImgLayout il(cam->width, cam->height, aux);
     v.depth_key = at<uint32_t>(b->geom, gl.depth_key);
     v.tiles = at<uint32_t>(b->geom, gl.tiles);
     v.flags = at<uint32_t>(b->geom, gl.flags);
@@ -288,8 +292,10 @@ Views views(const gsr_camera* cam, long long n, const gsr_buffers* b) {
     v.term = at<uint32_t>(b->image, il.term);
     v.final_T = at<float>(b->image, il.final_T);
     v.accum = at<float>(b->image, il.accum);
+    v.accum_z = aux ? at<float>(b->image, il.accum_z) : nullptr;
     if (b->binning) {
-        const BinLayout bl(b->capacity, (long long)ImgLayout::tile_count(cam->width, cam->height));
+        const BinLayout bl(b->capacity, (long long)ImgLayout::tile_count(cam->width, cam->height), aux);
+        v.ckz = aux ? at<float>(b->binning, bl.ckz) : nullptr;
         v.ck = at<float4>(b->binning, bl.ck);
         v.ck_bytes = bl.ckm - bl.ck;
         v.kA = at<uint32_t>(b->binning, bl.kA);
@@ -333,6 +339,10 @@ struct FwdJob {
     int ty0 = 0, ty1 = 0, gx = 0, gy = 0;
     int vgy = 0, vh = 0;  // views mode: tile rows per view band, pixel rows per view (0: one image)
     bool rows_counted = false;  // F1 wrote the row-bucketed binning's pass-A counts (run_preprocess)
+    const gsr_aux_out* aux = nullptr;  // gsr_forward_aux: the depth / alpha outputs (full image)
+    uint32_t aux_bits() const {
+        return aux ? kBufAux | ((rs->flags & GSR_FLAG_INVDEPTH) ? kBufInvDepth : 0u) : 0u;
+    }
 };
 
 // Allocations (geometry from the caller when geom_ready), range / counter clears, background
@@ -349,11 +359,11 @@ int fwd_phase1(FwdJob& j, gsr_alloc_fn alloc_geom, gsr_alloc_fn alloc_image, voi
     j.gy = div_up(H, kTile);
     band(cam, rs, &j.ty0, &j.ty1);
     std::memset(bufs, 0, sizeof *bufs);
-    bufs->layout = GSR_LAYOUT_TAG | (use_presort(j.n, j.gx, j.gy) ? kBufPresort : 0u);
+    bufs->layout = GSR_LAYOUT_TAG | (use_presort(j.n, j.gx, j.gy) ? kBufPresort : 0u) | j.aux_bits();
     bufs->num_rendered = -1;
     bufs->n_local = (int32_t)j.n;
     bufs->geom = alloc_geom(ctx, GeomLayout(j.n).total);
-    bufs->image = alloc_image(ctx, ImgLayout(W, H).total);
+    bufs->image = alloc_image(ctx, ImgLayout(W, H, j.aux != nullptr).total);
     if (!bufs->geom || !bufs->image) return fail(-2, "allocation failed (geometry/image)");
     const ImgLayout il(W, H);
     const Views v = views(cam, j.n, bufs);
@@ -392,14 +402,15 @@ int fwd_phase2(FwdJob& j, long long cap, gsr_alloc_fn alloc_binning, void* ctx, 
     gsr_buffers* bufs = j.bufs;
     if (cap > INT32_MAX) return fail(-3, "num_rendered overflow (%lld)", cap);
     bufs->capacity = (int32_t)cap;
-    bufs->binning = alloc_binning(ctx, BinLayout(cap, (long long)ImgLayout::tile_count(cam->width, cam->height)).total);
+    bufs->binning = alloc_binning(ctx, BinLayout(cap, (long long)ImgLayout::tile_count(cam->width, cam->height),
+                                                 j.aux != nullptr).total);
     if (!bufs->binning) return fail(-2, "allocation failed (binning, %lld instances)", cap);
     const int tiles = j.gx * j.gy, ntiles = (j.ty1 - j.ty0) * j.gx;
     // Row-bucketed binning when the image fits it and the register form takes the per-tile depth
     // order (it leaves a tile's entries unordered, which that form does not mind); recorded in the
     // buffers so that every later view of them (backward, accessors) finds the same arrays.
     const bool scanned = use_rb_binning(j.n, j.gx, j.gy);  // phase 1 ran the three-kernel scan
-    bufs->layout = expected_layout(j.n, j.gx, j.gy, cap, ntiles);
+    bufs->layout = expected_layout(j.n, j.gx, j.gy, cap, ntiles) | j.aux_bits();
     const Views v = views(cam, j.n, bufs);
     if (v.presort)
         GSR_STAGE(GSR_STAGE_DUPLICATE, launch_duplicate_ranked(v.rtiles, v.rrect, v.rect, (int)j.n, j.gx, j.ty0,
@@ -453,10 +464,18 @@ int fwd_phase2(FwdJob& j, long long cap, gsr_alloc_fn alloc_binning, void* ctx, 
                                                                v.free_v, stream),
                   "per-tile depth order");
     }
-    GSR_STAGE(GSR_STAGE_BLEND_FWD, launch_blend_forward(*cam, j.rs->bg, j.ty0, j.ty1, v.ranges, v.sorted_gid, v.rec,
-                                                        j.out_color, v.final_T, v.accum, v.term, v.ck, cap, stream,
-                                                        j.vgy, j.vh, v.mk),
-              "blend forward");
+    if (j.aux)
+        GSR_STAGE(GSR_STAGE_BLEND_FWD, launch_blend_forward_aux(*cam, j.rs->bg, v.ranges, v.sorted_gid, v.rec,
+                                                                v.depth_key, (j.rs->flags & GSR_FLAG_INVDEPTH) != 0,
+                                                                j.out_color, j.aux->depth, j.aux->alpha, v.final_T,
+                                                                v.accum, v.accum_z, v.term, v.ck, v.ckz, cap, stream,
+                                                                v.mk),
+                  "blend forward (aux)");
+    else
+        GSR_STAGE(GSR_STAGE_BLEND_FWD, launch_blend_forward(*cam, j.rs->bg, j.ty0, j.ty1, v.ranges, v.sorted_gid,
+                                                            v.rec, j.out_color, v.final_T, v.accum, v.term, v.ck, cap,
+                                                            stream, j.vgy, j.vh, v.mk),
+                  "blend forward");
     return 0;
 }
 
@@ -500,7 +519,7 @@ int run_preprocess(const gsr_camera* cam, const gsr_gaussians* gs, int ty0, int 
 // B1 (+ the per-Gaussian gather into grad2d): shared by every backward entry point.
 int blend_backward(const gsr_camera* cam, const gsr_raster_settings* rs, const gsr_buffers* bufs, const float* dL_dpix,
                    gsr_alloc_fn alloc_scratch, void* ctx, float* grad2d, hipStream_t stream, bool debug, int vgy = 0,
-                   int vh = 0) {
+                   int vh = 0, const gsr_aux_grads* aux = nullptr) {
     if (!bufs || !bufs->geom || !bufs->image || !bufs->binning || !dL_dpix) return fail(-1, "missing forward buffers / dL_dpix");
     if (!grad2d) return fail(-1, "null grad2d");
     const long long n = bufs->n_local, cap = bufs->capacity;
@@ -510,6 +529,22 @@ int blend_backward(const gsr_camera* cam, const gsr_raster_settings* rs, const g
     if (int e = check_layout(cam, ty0, ty1, bufs)) return e;
     const Views v = views(cam, n, bufs);
     if (!alloc_scratch) return fail(-1, "null scratch allocator");
+    if (aux) {  // gsr_backward_aux (full image, aux buffers: checked by the caller)
+        float* partial = static_cast<float*>(alloc_scratch(ctx, PartLayout(cap, true).total));
+        if (!partial) return fail(-2, "allocation failed (scratch, %lld instances)", cap);
+        const bool inv = (bufs->layout & kBufInvDepth) != 0;
+        GSR_STAGE(GSR_STAGE_MISC, launch_clear_flags(partial, cap, stream), "clear partial flags");
+        GSR_STAGE(GSR_STAGE_BLEND_BWD, launch_blend_backward_aux(*cam, rs->bg, v.ranges, v.sorted_gid, v.rect, v.rec,
+                                                                 v.depth_key, inv, v.final_T, v.accum, v.accum_z,
+                                                                 dL_dpix, aux->dL_ddepth, aux->dL_dalpha, partial, cap,
+                                                                 v.term, v.ck, v.ckz, stream, v.mk),
+                  "blend backward (aux)");
+        GSR_STAGE(GSR_STAGE_GATHER, launch_gather_grad2d(v.offsets, partial, v.rec, cam->width, cam->height, cap,
+                                                         (int)n, v.presort ? v.rrect : nullptr, grad2d, stream, 1,
+                                                         true),
+                  "gather grad2d (aux)");
+        return 0;
+    }
     // band launches split each (tile, chunk) of B1 over `split` waves by stripe, one partial
     // entry per (instance, part)
     int split = b1_split(cam->width, cam->height, ty0, ty1, vgy);
@@ -619,23 +654,29 @@ size_t gsr_binning_bytes(int32_t capacity, int32_t w, int32_t h) {
 }
 size_t gsr_image_bytes(int32_t w, int32_t h) { return ImgLayout(w, h).total; }
 size_t gsr_scratch_bytes(int32_t capacity) { return PartLayout(capacity).total; }
+size_t gsr_binning_bytes_aux(int32_t capacity, int32_t w, int32_t h) {
+    return BinLayout(capacity, (long long)ImgLayout::tile_count(w, h), true).total;
+}
+size_t gsr_image_bytes_aux(int32_t w, int32_t h) { return ImgLayout(w, h, true).total; }
+size_t gsr_scratch_bytes_aux(int32_t capacity) { return PartLayout(capacity, true).total; }
 size_t gsr_exchange_block_bytes(int32_t pair_cap) { return exchange_block_bytes(pair_cap > 0 ? pair_cap : 0); }
 size_t gsr_shard_state_bytes(int32_t P, int32_t nbands, int32_t pair_cap) {
     (void)pair_cap;
     return ShardLayout(P, nbands > 0 ? nbands : 1).total;
 }
 
-int gsr_forward(const gsr_camera* cam, const gsr_gaussians* gs, const gsr_raster_settings* rs,
-                float* out_color, int32_t* radii, gsr_alloc_fn alloc_geom, gsr_alloc_fn alloc_binning,
-                gsr_alloc_fn alloc_image, void* ctx, gsr_buffers* bufs, void* stream_) {
-    g_err.clear();
-    if (int e = validate(cam, gs, rs)) return e;
+// gsr_forward / gsr_forward_aux (aux != nullptr: validated by the caller)
+static int forward_one(const gsr_camera* cam, const gsr_gaussians* gs, const gsr_raster_settings* rs,
+                       float* out_color, int32_t* radii, gsr_alloc_fn alloc_geom, gsr_alloc_fn alloc_binning,
+                       gsr_alloc_fn alloc_image, void* ctx, gsr_buffers* bufs, void* stream_,
+                       const gsr_aux_out* aux) {
     if (!out_color || (gs->P > 0 && !radii) || !bufs || !alloc_geom || !alloc_binning || !alloc_image)
         return fail(-1, "null output / allocator");
     if (rs->max_rendered < 0) return fail(-1, "negative max_rendered");
     hipStream_t stream = (hipStream_t)stream_;
     const bool debug = (rs->flags & GSR_FLAG_DEBUG) != 0;
     FwdJob j{cam, rs, out_color, bufs};
+    j.aux = aux;
     j.n = gs->P;
     const bool exact = rs->max_rendered == 0;
     if (int e = fwd_phase1(j, alloc_geom, alloc_image, ctx, stream, debug, false, [&](const Views& v) {
@@ -660,6 +701,27 @@ int gsr_forward(const gsr_camera* cam, const gsr_gaussians* gs, const gsr_raster
         bufs->num_rendered = (int32_t)ksum;
     }
     return fwd_phase2(j, cap, alloc_binning, ctx, stream, debug);
+}
+
+int gsr_forward(const gsr_camera* cam, const gsr_gaussians* gs, const gsr_raster_settings* rs,
+                float* out_color, int32_t* radii, gsr_alloc_fn alloc_geom, gsr_alloc_fn alloc_binning,
+                gsr_alloc_fn alloc_image, void* ctx, gsr_buffers* bufs, void* stream_) {
+    g_err.clear();
+    if (int e = validate(cam, gs, rs)) return e;
+    return forward_one(cam, gs, rs, out_color, radii, alloc_geom, alloc_binning, alloc_image, ctx, bufs, stream_,
+                       nullptr);
+}
+
+int gsr_forward_aux(const gsr_camera* cam, const gsr_gaussians* gs, const gsr_raster_settings* rs,
+                    float* out_color, int32_t* radii, gsr_alloc_fn alloc_geom, gsr_alloc_fn alloc_binning,
+                    gsr_alloc_fn alloc_image, void* ctx, gsr_buffers* bufs, void* stream_, const gsr_aux_out* aux) {
+    g_err.clear();
+    if (int e = validate(cam, gs, rs)) return e;
+    if (!aux || !aux->depth || !aux->alpha) return fail(-1, "aux: null gsr_aux_out / depth / alpha output");
+    if (rs->tile_y0 > 0 || rs->tile_y1 < div_up(cam->height, kTile))
+        return fail(-1, "aux: full images only (tile rows [%d, %d) of %d are a band)", rs->tile_y0, rs->tile_y1,
+                    div_up(cam->height, kTile));
+    return forward_one(cam, gs, rs, out_color, radii, alloc_geom, alloc_binning, alloc_image, ctx, bufs, stream_, aux);
 }
 
 int gsr_read_num_rendered(const gsr_camera* cam, const gsr_buffers* bufs, int32_t* num_rendered, void* stream_) {
@@ -857,6 +919,40 @@ int gsr_backward(const gsr_camera* cam, const gsr_gaussians* gs, const gsr_raste
                                                                    stored_flags(cam, rs, v.flags), grad2d,
                                                                    grad_out(grads), stream),
               "preprocess backward");
+    return 0;
+}
+
+int gsr_backward_aux(const gsr_camera* cam, const gsr_gaussians* gs, const gsr_raster_settings* rs,
+                     const gsr_buffers* bufs, const float* dL_dpix, gsr_alloc_fn alloc_scratch, void* ctx,
+                     const gsr_grads* grads, void* stream_, const gsr_aux_grads* aux) {
+    g_err.clear();
+    if (int e = validate(cam, gs, rs)) return e;
+    if (!aux) return fail(-1, "aux: null gsr_aux_grads");
+    const int gy = div_up(cam->height, kTile);
+    if (rs->tile_y0 > 0 || rs->tile_y1 < gy)
+        return fail(-1, "aux: full images only (tile rows [%d, %d) of %d are a band)", rs->tile_y0, rs->tile_y1, gy);
+    if (gs->P == 0) return 0;
+    if (int e = check_grads(gs, grads)) return e;
+    if (!bufs || bufs->n_local != gs->P) return fail(-1, "forward buffers do not match the Gaussians");
+    if (int e = check_layout(cam, 0, gy, bufs)) return e;  // before any allocation
+    if (!(bufs->layout & kBufAux))
+        return fail(GSR_ERR_LAYOUT, "gsr_backward_aux: gsr_buffers.layout = 0x%08x is not gsr_forward_aux's "
+                                    "(no GSR_LAYOUT_AUX): the buffers hold no depth sums",
+                    bufs->layout);
+    const bool inv = (rs->flags & GSR_FLAG_INVDEPTH) != 0;
+    if (inv != ((bufs->layout & kBufInvDepth) != 0))
+        return fail(GSR_ERR_LAYOUT, "gsr_backward_aux: GSR_FLAG_INVDEPTH is %s but the forward ran %s it",
+                    inv ? "set" : "clear", inv ? "without" : "with");
+    hipStream_t stream = (hipStream_t)stream_;
+    const bool debug = (rs->flags & GSR_FLAG_DEBUG) != 0;
+    if (!alloc_scratch) return fail(-1, "null scratch allocator");
+    float* grad2d = static_cast<float*>(alloc_scratch(ctx, sizeof(float) * kPart * (size_t)gs->P));
+    if (!grad2d) return fail(-2, "allocation failed (grad2d, P=%d)", gs->P);
+    if (int e = blend_backward(cam, rs, bufs, dL_dpix, alloc_scratch, ctx, grad2d, stream, debug, 0, 0, aux)) return e;
+    const Views v = views(cam, gs->P, bufs);
+    GSR_STAGE(GSR_STAGE_PREPROCESS_BWD, launch_preprocess_backward(*cam, gauss_in(gs), 0, gs->P, v.depth_key, v.flags,
+                                                                   grad2d, grad_out(grads), stream, inv ? 2 : 1),
+              "preprocess backward (aux)");
     return 0;
 }
 

@@ -181,8 +181,44 @@ __device__ __forceinline__ float pair_alpha_keep(float e, float L, float& oG, bo
 #ifndef GSR_F6_WPE
 #define GSR_F6_WPE 8
 #endif
-template <int NW>
-__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 2 ? GSR_F6_WPE : 1))) void blend_forward_kernel(const BlendGeom geo,
+// Depth / alpha channel (gsr_forward_aux, gsr_backward_aux).  The aux variants of F6 and B1 are the
+// same kernels instantiated with one more trailing argument (the pack AX = {F6Aux} / {B1Aux}); with
+// the pack empty every `if constexpr (AUX)` block drops out and the kernel -- arguments, registers,
+// LDS, instructions -- is the plain one.  v_i, the value the channel blends, is the Gaussian's
+// view-space depth (the float whose bits are its depth key) or its reciprocal; it is staged in LDS
+// beside the record at batch load (the 48-byte record has no free lane).
+struct F6Aux {
+    const uint32_t* depth_key;  // per Gaussian: bits of the f32 view-space depth
+    float* out_depth;           // H x W: sum w v
+    float* out_alpha;           // H x W: sum w (= 1 - final T)
+    float* accum_z;             // H x W: the depth sum, for B1
+    float* ckz;                 // per checkpoint slot 256 floats: the depth sum so far
+    int inv;                    // v = 1 / z
+};
+struct B1Aux {
+    const uint32_t* depth_key;
+    const float* accum_z;
+    const float* dL_ddepth;  // H x W or nullptr (zero)
+    const float* dL_dalpha;  // H x W or nullptr (zero)
+    const float* ckz;
+    float* pz;               // per partial entry: the tenth moment, sum w dL/ddepth
+    int inv;
+};
+template <class T>
+__device__ __forceinline__ T aux_arg() { return T{}; }
+template <class T>
+__device__ __forceinline__ T aux_arg(const T& a) { return a; }
+__device__ __forceinline__ float aux_value(uint32_t key, int inv) {
+    const float z = __uint_as_float(key);
+    return inv ? 1.0f / z : z;
+}
+// The aux F6 variants hold one more accumulator per pixel: GSR_F6_AUX_WPE waves per SIMD for the
+// two-wave form (DESIGN.md "Depth and alpha outputs" has the compiler's resource report)
+#ifndef GSR_F6_AUX_WPE
+#define GSR_F6_AUX_WPE 7
+#endif
+template <int NW, class... AX>
+__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 2 ? (sizeof...(AX) ? GSR_F6_AUX_WPE : GSR_F6_WPE) : 1))) void blend_forward_kernel(const BlendGeom geo,
                                                                 const uint2* __restrict__ ranges,
                                                                 const uint32_t* __restrict__ sorted_gid,
                                                                 const float4* __restrict__ rec,
@@ -191,7 +227,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 2
                                                                 float* __restrict__ accum,
                                                                 uint32_t* __restrict__ term,
                                                                 float4* __restrict__ ck,
-                                                                uint8_t* __restrict__ mk) {
+                                                                uint8_t* __restrict__ mk, const AX... axp) {
+    constexpr bool AUX = sizeof...(AX) > 0;
+    static_assert(sizeof...(AX) <= 1, "one aux argument");
+    const F6Aux ax = aux_arg<F6Aux>(axp...);
     constexpr int PPL = kPPL / NW;
     // records per batch: one per thread, or (GSR_F6_BATCH4 = 128) four waves sharing the two-wave
     // kernel's 128-record batches -- the same live-stripe refresh points, so the same chunks
@@ -201,6 +240,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 2
     __shared__ float4 srec[BATCH * 3];
     __shared__ uint32_t smk[BATCH];
     __shared__ uint32_t slive[NW];
+    __shared__ float svz[AUX ? BATCH : 1];  // aux: the batch's v_i (unused, so absent, otherwise)
     const int tl = xcd_tile(blockIdx.x, geo.nwg);  // band-local tile index
     const int tile = tl + geo.ty0 * geo.grid_x;
     const int tx = tile % geo.grid_x, ty = tile / geo.grid_x;
@@ -210,15 +250,25 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 2
     const int view = ty / geo.vgy, tyl = ty - view * geo.vgy;  // tile row inside its view's band
     const float bx0 = (float)(tx * kTile), by0 = (float)(tyl * kTile);
     float pfy[PPL], T[PPL], C0[PPL], C1[PPL], C2[PPL];
+    float Z[PPL];  // aux: sum w v
 #pragma unroll
     for (int p = 0; p < PPL; ++p) {
         const int pyl = tyl * kTile + (lane >> 4) + 4 * (w * PPL + p);
         pfy[p] = (float)pyl;
         T[p] = (px < geo.W && pyl < geo.vh) ? 1.0f : -1.0f;
         C0[p] = C1[p] = C2[p] = 0.0f;
+        Z[p] = 0.0f;
     }
     const uint2 range = ranges[tile];
     const int n = (int)(range.y - range.x);
+    // aux: the depth channel is accumulated relative to vref, the value of the tile's first (nearest)
+    // record: Zc = sum w (v - vref), depth = Zc + vref (1 - T_final).  A pixel's values differ little
+    // along its depth-sorted list, so the f32 sum then rounds at the size of the depth spread, not of
+    // the depth -- B1 replays the sum as a running difference and inherits its rounding error whole.
+    float vref = 0.0f;
+    if constexpr (AUX) {
+        if (n > 0) vref = aux_value(ax.depth_key[sorted_gid[range.x]], ax.inv);
+    }
     // B1 chunk checkpoints: (T, colour sum) of every pixel where a chunk starts.  `work` counts
     // the (record, stripe) pairs of the current chunk: a record's stripe mask against the stripes
     // live (anywhere in the tile) at the start of its batch -- block-uniform, so every wave takes
@@ -238,6 +288,9 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 2
         for (int p = 0; p < PPL; ++p) {
             const bool on = (lv >> p) & 1u;  // wave-uniform
             if (on) dst[64 * (w * PPL + p) + lane] = make_float4(T[p], C0[p], C1[p], C2[p]);
+            if constexpr (AUX) {
+                if (on) ax.ckz[(size_t)slot * 256 + 64 * (w * PPL + p) + lane] = Z[p];
+            }
             if (lane == 0) ckm[4 * (size_t)slot + w * PPL + p] = on ? 1 : 0;
         }
     };
@@ -263,6 +316,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 2
             for (int p = 0; p < PPL; ++p) {
                 const int i = 64 * (w * PPL + p) + lane;
                 ckt[256 * k + i] = ckt[512 * k + i];
+                if constexpr (AUX) {  // the slot's depth words move with it
+                    float* const ckzt = ax.ckz + ck_slot_of(geo.ck_fixed, range.x, tl, 1) * 256 - 256;
+                    ckzt[256 * k + i] = ckzt[512 * k + i];
+                }
                 if (lane == 0) ckmt[4 * k + w * PPL + p] = ckmt[8 * k + w * PPL + p];
             }
             if (tid == 0) table[k] = table[2 * k];
@@ -297,6 +354,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 2
             srec[3 * tid + 1] = r1;
             srec[3 * tid + 2] = r2;
             smk[tid] = stripe_mask(r0, r1, r2, bx0, by0);
+            if constexpr (AUX) svz[tid] = aux_value(ax.depth_key[g], ax.inv) - vref;
             mk[range.x + base + tid] = (uint8_t)smk[tid];  // B1's visit filter
         } else if (tid < BATCH) {
             smk[tid] = 0u;
@@ -365,6 +423,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 2
                         C0[0] = fmaf(a1.z, wgt, C0[0]);
                         C1[0] = fmaf(a1.w, wgt, C1[0]);
                         C2[0] = fmaf(a2.x, wgt, C2[0]);
+                        if constexpr (AUX) Z[0] = fmaf(svz[ka], wgt, Z[0]);
                         T[0] = ok ? tT : -fabsf(T[0]);
                     }
                     if (two) {
@@ -375,6 +434,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 2
                         C0[0] = fmaf(b1.z, wgt, C0[0]);
                         C1[0] = fmaf(b1.w, wgt, C1[0]);
                         C2[0] = fmaf(b2.x, wgt, C2[0]);
+                        if constexpr (AUX) Z[0] = fmaf(svz[kb], wgt, Z[0]);
                         T[0] = ok ? tT : -fabsf(T[0]);
                     }
                     const int before = visited;
@@ -396,6 +456,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 2
                 const float dx = r0.x - pfx;
                 const float bdx = r0.w * dx;
                 const float K = fmaf(r0.z * dx, dx, r2.w);  // column part of the exponent + log2 o
+                float vz = 0.0f;
+                if constexpr (AUX) vz = svz[k];
 #pragma unroll
                 for (int p = 0; p < PPL; ++p) {
                     // No per-stripe branch: a culled stripe's pixels all get alpha 0 (exact test),
@@ -415,6 +477,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 2
                     C0[p] = fmaf(r1.z, wgt, C0[p]);
                     C1[p] = fmaf(r1.w, wgt, C1[p]);
                     C2[p] = fmaf(r2.x, wgt, C2[p]);
+                    if constexpr (AUX) Z[p] = fmaf(vz, wgt, Z[p]);
                     T[p] = ok ? tT : -fabsf(T[p]);
                 }
                 if ((++visited & 7) == 0) {
@@ -454,6 +517,11 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 2
             oc[pix] = C0[p] + Tf * geo.bg0;
             oc[npix + pix] = C1[p] + Tf * geo.bg1;
             oc[2 * npix + pix] = C2[p] + Tf * geo.bg2;
+            if constexpr (AUX) {  // one image (aux launches have no views): no background term
+                ax.accum_z[pix] = Z[p];  // centred (B1 takes the same vref)
+                ax.out_depth[pix] = fmaf(vref, 1.0f - Tf, Z[p]);
+                ax.out_alpha[pix] = 1.0f - Tf;
+            }
         }
     }
 }
@@ -476,11 +544,14 @@ static_assert(kParkSlot % 32 == 8 && kParkSlot % 4 == 0, "flush banks / float4 a
 // The parked records' batch indices ride in one scalar word (6 bits per slot: `kpack`); the
 // flush lane of slot s reads its record's emission index from the batch's jl table (`sjl`,
 // written once per batch), so a record costs no per-record readlane / LDS write for it.
+// AUX: a tenth moment (row slot 9, flush lanes 36-39: the second ds_read_b32 lane group, whose
+// banks 8 s + 9 + 12 i are distinct as well) goes to its own per-entry array pz.
+template <bool AUX = false>
 __device__ __forceinline__ void park_flush(const float* qpark, const uint32_t* sjl, uint32_t kpack, int parked,
-                                           float* p8f, float* p1, uint8_t* fl, int lane) {
+                                           float* p8f, float* p1, uint8_t* fl, int lane, float* pz = nullptr) {
     __syncthreads();  // one-wave block: orders the quad leaders' LDS writes before the reads
     const int slot = lane & 3, c = lane >> 2;
-    if (c < 9 && slot < parked) {
+    if (c < (AUX ? 10 : 9) && slot < parked) {
         const float* q = qpark + slot * kParkSlot + c;
         // -0 is the identity of IEEE addition, so the first add of each chain folds into a move
         float t[4] = {-0.f, -0.f, -0.f, -0.f};
@@ -489,6 +560,7 @@ __device__ __forceinline__ void park_flush(const float* qpark, const uint32_t* s
         const uint32_t j = sjl[(kpack >> (6 * slot)) & 63u];
         if (j != 0xFFFFFFFFu) {  // an entry past the capacity (binning overflow) has none
             float* dst = c < 8 ? p8f + 8 * (size_t)j + c : p1 + j;
+            if constexpr (AUX) dst = c == 9 ? pz + j : dst;
             *dst = (t[0] + t[1]) + (t[2] + t[3]);
             if (c == 8) fl[j] = 1;  // the gather reads flagged entries only
         }
@@ -545,8 +617,13 @@ static_assert(kB1Win == 4 || kB1Win == 16, "B1 window: 4 or 16 mask bytes per la
 // previous record's work (2x unrolled, no register copies) -- with ~3 one-wave blocks per SIMD on a
 // band's 1020 tiles the LDS latency per record is exposed, where on full images other waves hide
 // it (round 4: the same prefetch at full occupancy measured 0.456 vs 0.447 ms).
-template <int SPW, bool PF = false>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PF ? 4 : (SPW == 4 ? 6 : 8)))) void blend_backward_kernel(const BlendGeom geo,
+// The aux B1 variants (SPW = 4 only) keep dL/ddepth per pixel and a tenth moment: GSR_B1_AUX_WPE
+// waves per SIMD (DESIGN.md "Depth and alpha outputs")
+#ifndef GSR_B1_AUX_WPE
+#define GSR_B1_AUX_WPE 5
+#endif
+template <int SPW, bool PF = false, class... AX>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PF ? 4 : (SPW == 4 ? (sizeof...(AX) ? GSR_B1_AUX_WPE : 6) : 8)))) void blend_backward_kernel(const BlendGeom geo,
                                                             const uint2* __restrict__ ranges,
                                                             const uint32_t* __restrict__ sorted_gid,
                                                             const uint4* __restrict__ rect,
@@ -559,7 +636,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PF ? 4 : (SP
                                                             uint8_t* __restrict__ fl,
                                                             const uint32_t* __restrict__ term,
                                                             const float4* __restrict__ ck,
-                                                            const uint8_t* __restrict__ mk) {
+                                                            const uint8_t* __restrict__ mk, const AX... axp) {
+    constexpr bool AUX = sizeof...(AX) > 0;
+    static_assert(sizeof...(AX) <= 1 && (!AUX || SPW == 4), "one aux argument, full-image B1 only");
+    const B1Aux ax = aux_arg<B1Aux>(axp...);
+    __shared__ float svz[AUX ? 64 : 1];  // aux: the batch's v_i (unused, so absent, otherwise)
     // One block of LDS with srec first: the record fields then sit within the immediate offsets
     // of the record reads (8-bit dword offsets of ds_read2), so a record costs no address add.
     __shared__ struct {
@@ -601,6 +682,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PF ? 4 : (SP
     // no such chunk for this tile, or every pixel had finished before it
     if (start_u >= (uint32_t)n_all || start_u >= tend) return;
     const int start = (int)start_u;
+    float vref = 0.0f;  // aux: F6's centre of the tile's depth values (its first record's)
+    if constexpr (AUX) vref = aux_value(ax.depth_key[sorted_gid[range.x]], ax.inv);
     const uint32_t next = chunk + 1 < kMaxChunks ? table[chunk + 1] : 0xFFFFFFFFu;
     const int n = next < (uint32_t)n_all ? (int)next : n_all;
     const int tx = tile % geo.grid_x, ty = tile / geo.grid_x;
@@ -619,6 +702,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PF ? 4 : (SP
     dL_dpix += (size_t)view * 3 * npix;
     // R = S . dL/dpix - Sp + T_final bg . dL/dpix: the colour term behind the current record
     float pfy[SPW], T[SPW], R[SPW], dp0[SPW], dp1[SPW], dp2[SPW];
+    // aux: dL/ddepth of the pixel, and v0 = its alpha-weighted mean of the (vref-centred) depth values.
+    // The depth channel is replayed centred on vref + v0: sum_{j>k} w_j v_j = sum_{j>k} w_j (v_j - v0) + v0 (T_{k+1} - T_final) for
+    // any constant v0, so with v'_j = v_j - v0 the channel is a colour v' over a background -v0
+    //   dL/dalpha_k (depth) = dpz (T_k v'_k - (sum_{j>k} w_j v'_j - v0 T_final) / (1 - alpha_k)).
+    // R then carries terms of the size of the depth spread within the pixel instead of the depth
+    // itself (the values differ little along a list, and R is a running difference: SURVEY B.4).
+    float dpz[SPW], v0[SPW], azS[SPW], azT[SPW], azA[SPW];
 #pragma unroll
     for (int p = 0; p < SPW; ++p) {
         const int pyl = tyl * kTile + row + 4 * (sp0 + p);
@@ -632,6 +722,20 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PF ? 4 : (SP
         const float sdp = in ? accum[pix] * dp0[p] + accum[npix + pix] * dp1[p] + accum[2 * npix + pix] * dp2[p]
                              : 0.0f;
         R[p] = sdp + Tfin * (geo.bg0 * dp0[p] + geo.bg1 * dp1[p] + geo.bg2 * dp2[p]);
+        dpz[p] = 0.0f;
+        if constexpr (AUX) {
+            // the depth channel is a fourth colour without background; alpha = 1 - T_final, so its
+            // gradient enters like a background of -dL/dalpha (both added to R below, once the
+            // chunk's start is known)
+            dpz[p] = in && ax.dL_ddepth ? ax.dL_ddepth[pix] : 0.0f;
+            azA[p] = in && ax.dL_dalpha ? ax.dL_dalpha[pix] : 0.0f;
+            azS[p] = in ? ax.accum_z[pix] : 0.0f;
+            azT[p] = Tfin;
+            const float atot = 1.0f - Tfin;
+            v0[p] = atot > 1e-6f ? azS[p] / atot : 0.0f;
+        } else {
+            v0[p] = azS[p] = azT[p] = azA[p] = 0.0f;
+        }
         T[p] = in ? 1.0f : -1.0f;
     }
     if (chunk > 0) {  // resume from F6's checkpoint: T, and R less dL/dpix . (colour sum so far)
@@ -646,9 +750,21 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PF ? 4 : (SP
                 const float4 c4 = src[64 * (sp0 + p) + col + 16 * row];  // F6's lane of this pixel
                 T[p] = c4.x;
                 R[p] -= fmaf(c4.y, dp0[p], fmaf(c4.z, dp1[p], c4.w * dp2[p]));
+                if constexpr (AUX) azS[p] -= ax.ckz[slot * 256 + 64 * (sp0 + p) + col + 16 * row];
             } else {
                 T[p] = -1.0f;
             }
+        }
+    }
+    if constexpr (AUX) {
+        // the depth and alpha terms of R at this chunk's start (azS: the depth sum from here on).  Both
+        // products are exact zeros when the aux gradients are absent, and R is then the plain kernel's,
+        // bit for bit.
+#pragma unroll
+        for (int p = 0; p < SPW; ++p) {
+            const float Tst = chunk > 0 ? fabsf(T[p]) : 1.0f;
+            const float rem = azS[p] - v0[p] * (Tst - azT[p]);  // sum over the records ahead of w (v - v0)
+            R[p] = R[p] + ((rem - (v0[p] + vref) * azT[p]) * dpz[p] - azT[p] * azA[p]);
         }
     }
     // F6 wrote the stripe mask of every entry it loaded, all before its termination index tend;
@@ -735,6 +851,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PF ? 4 : (SP
             srec[3 * lane + 0] = r[0];
             srec[3 * lane + 1] = r[1];
             srec[3 * lane + 2] = r[2];
+            if constexpr (AUX) svz[lane] = aux_value(ax.depth_key[g], ax.inv) - vref;
             smask = lds.smv[lane];
         }
         sjl[lane] = jl;
@@ -744,7 +861,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PF ? 4 : (SP
         uint32_t kpack = 0;  // batch slots of the parked records, 6 bits each
         // one visited record (batch slot k): its stripes, then its moments parked / flushed;
         // true when every pixel of the tile has finished
-        auto record = [&](const int k, const float4 r0, const float4 r1, const float4 r2) -> bool {
+        auto record = [&](const int k, const float4 r0, const float4 r1, const float4 r2, const float vz) -> bool {
             const uint32_t m = (uint32_t)__builtin_amdgcn_readlane((int)smask, k) & live;
             const float dx = r0.x - pfx;
             const float bdx = r0.w * dx;
@@ -753,12 +870,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PF ? 4 : (SP
             // the first stripe's adds / FMAs into these fold into plain moves / multiplies
             // without fast-math; +0 would keep them (0 + -0 = +0)
             float s0 = -0.f, sy = -0.f, syy = -0.f, g0 = -0.f, g1 = -0.f, g2 = -0.f;
+            float gz = -0.f;  // aux: sum w dL/ddepth
             bool any = false;
             // one contributing (pixel, record) pair of stripe p into the record's moments
             auto contribute = [&](const int p, const float a, const float w, const float oG, const float dy) {
                 any = true;
                 const float one_m = 1.0f - a;
-                const float cdp = fmaf(r1.z, dp0[p], fmaf(r1.w, dp1[p], r2.x * dp2[p]));
+                float cdp = fmaf(r1.z, dp0[p], fmaf(r1.w, dp1[p], r2.x * dp2[p]));
+                if constexpr (AUX) {
+                    cdp = fmaf(vz - v0[p], dpz[p], cdp);
+                    gz = fmaf(w, dpz[p], gz);
+                }
                 R[p] = fmaf(-w, cdp, R[p]);
                 const float dLda = fmaf(T[p], cdp, -R[p] * __builtin_amdgcn_rcpf(one_m));
                 g0 = fmaf(w, dp0[p], g0);
@@ -819,7 +941,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PF ? 4 : (SP
             if (__any(any)) {
                 // the quad shares dx: reduce the six column sums (12 DPP adds, not 18 for the
                 // nine dx-weighted moments of a row-major quad), then apply dx once
-                float u[6] = {s0, sy, syy, g0, g1, g2};
+                float u[AUX ? 7 : 6] = {s0, sy, syy, g0, g1, g2};
+                if constexpr (AUX) u[6] = gz;
                 quad_reduce(u);
                 const float sx = u[0] * dx;
                 float v[9] = {sx, u[1], sx * dx, u[1] * dx, u[2], u[0], u[3], u[4], u[5]};
@@ -828,10 +951,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PF ? 4 : (SP
                     *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[1], v[2], v[3]);
                     *reinterpret_cast<float4*>(dst + 4) = make_float4(v[4], v[5], v[6], v[7]);
                     dst[8] = v[8];
+                    if constexpr (AUX) dst[9] = u[6];
                 }
                 kpack |= (uint32_t)k << (6 * parked);
                 if (++parked == kPark) {
-                    park_flush(qpark, sjl, kpack, parked, p8f, p1, fl, lane);
+                    park_flush<AUX>(qpark, sjl, kpack, parked, p8f, p1, fl, lane, ax.pz);
                     parked = 0;
                     kpack = 0;
                 }
@@ -851,6 +975,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PF ? 4 : (SP
                 todo &= todo - 1;
                 float4 a0 = srec[3 * ka + 0], a1 = srec[3 * ka + 1], a2 = srec[3 * ka + 2];
                 float4 b0, b1, b2;
+                float za = 0.0f, zb = 0.0f;
+                if constexpr (AUX) za = svz[ka];
                 while (true) {
                     const int kb = todo ? __builtin_ctzll(todo) : -1;  // wave-uniform
                     if (kb >= 0) {
@@ -858,26 +984,30 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PF ? 4 : (SP
                         b0 = srec[3 * kb + 0];
                         b1 = srec[3 * kb + 1];
                         b2 = srec[3 * kb + 2];
+                        if constexpr (AUX) zb = svz[kb];
                     }
-                    if (record(ka, a0, a1, a2) || kb < 0) break;
+                    if (record(ka, a0, a1, a2, za) || kb < 0) break;
                     ka = todo ? __builtin_ctzll(todo) : -1;
                     if (ka >= 0) {
                         todo &= todo - 1;
                         a0 = srec[3 * ka + 0];
                         a1 = srec[3 * ka + 1];
                         a2 = srec[3 * ka + 2];
+                        if constexpr (AUX) za = svz[ka];
                     }
-                    if (record(kb, b0, b1, b2) || ka < 0) break;
+                    if (record(kb, b0, b1, b2, zb) || ka < 0) break;
                 }
             }
         } else {
             while (todo) {
                 const int k = __builtin_ctzll(todo);
                 todo &= todo - 1;
-                if (record(k, srec[3 * k + 0], srec[3 * k + 1], srec[3 * k + 2])) break;
+                float vz = 0.0f;
+                if constexpr (AUX) vz = svz[k];
+                if (record(k, srec[3 * k + 0], srec[3 * k + 1], srec[3 * k + 2], vz)) break;
             }
         }
-        if (parked) park_flush(qpark, sjl, kpack, parked, p8f, p1, fl, lane);
+        if (parked) park_flush<AUX>(qpark, sjl, kpack, parked, p8f, p1, fl, lane, ax.pz);
         __syncthreads();  // srec / qpark are rewritten by the next batch
     }
 }
@@ -979,6 +1109,50 @@ int launch_blend_backward(const gsr_camera& cam, const float bg[3], int ty0, int
     else
         hipLaunchKernelGGL(blend_backward_kernel<1>, dim3(blocks), dim3(64), 0, s, geo, ranges, sorted_gid, rect, rec,
                            final_T, accum, dL_dpix, p8, p1, fl, term, ck, mk);
+    return (int)hipGetLastError();
+}
+
+// The aux launches choose their instantiations by the image's tile count exactly as the plain ones
+// do (same batches, same chunk quota), so a forward's chunk table -- and with it every colour
+// gradient bit -- does not depend on whether the aux channel rides along.
+int launch_blend_forward_aux(const gsr_camera& cam, const float bg[3], const uint2* ranges,
+                             const uint32_t* sorted_gid, const float4* rec, const uint32_t* depth_key, bool inv,
+                             float* out_color, float* out_depth, float* out_alpha, float* final_T, float* accum,
+                             float* accum_z, uint32_t* term, float4* ck, float* ckz, long long cap, hipStream_t s,
+                             uint8_t* mk) {
+    const BlendGeom geo = make_geo(cam, bg, 0, div_up(cam.height, kTile), cap, 0, 0);
+    if (geo.nwg <= 0) return 0;
+    const F6Aux ax{depth_key, out_depth, out_alpha, accum_z, ckz, inv ? 1 : 0};
+    if (geo.nwg >= kF6BandTiles)
+        hipLaunchKernelGGL((blend_forward_kernel<kF6FullWaves, F6Aux>), dim3(geo.nwg), dim3(64 * kF6FullWaves), 0, s,
+                           geo, ranges, sorted_gid, rec, out_color, final_T, accum, term, ck, mk, ax);
+    else
+        hipLaunchKernelGGL((blend_forward_kernel<kF6BandWaves, F6Aux>), dim3(geo.nwg), dim3(64 * kF6BandWaves), 0, s,
+                           geo, ranges, sorted_gid, rec, out_color, final_T, accum, term, ck, mk, ax);
+    return (int)hipGetLastError();
+}
+
+int launch_blend_backward_aux(const gsr_camera& cam, const float bg[3], const uint2* ranges,
+                              const uint32_t* sorted_gid, const uint4* rect, const float4* rec,
+                              const uint32_t* depth_key, bool inv, const float* final_T, const float* accum,
+                              const float* accum_z, const float* dL_dpix, const float* dL_ddepth,
+                              const float* dL_dalpha, float* partial, long long cap, const uint32_t* term,
+                              const float4* ck, const float* ckz, hipStream_t s, const uint8_t* mk) {
+    const BlendGeom geo = make_geo(cam, bg, 0, div_up(cam.height, kTile), cap, 0, 0);
+    if (geo.nwg <= 0) return 0;
+    const PartLayout pl(cap, true);
+    char* base = reinterpret_cast<char*>(partial);
+    const int blocks = 8 * (geo.nwg / 8 + 1) * kMaxChunks;
+    auto* p8 = reinterpret_cast<float*>(base + pl.p8);
+    auto* p1 = reinterpret_cast<float*>(base + pl.p1);
+    auto* fl = reinterpret_cast<uint8_t*>(base + pl.fl);
+    const B1Aux ax{depth_key, accum_z, dL_ddepth, dL_dalpha, ckz, reinterpret_cast<float*>(base + pl.pz), inv ? 1 : 0};
+    if (GSR_B1_BAND_PREFETCH && geo.nwg < kF6BandTiles)
+        hipLaunchKernelGGL((blend_backward_kernel<4, true, B1Aux>), dim3(blocks), dim3(64), 0, s, geo, ranges,
+                           sorted_gid, rect, rec, final_T, accum, dL_dpix, p8, p1, fl, term, ck, mk, ax);
+    else
+        hipLaunchKernelGGL((blend_backward_kernel<4, false, B1Aux>), dim3(blocks), dim3(64), 0, s, geo, ranges,
+                           sorted_gid, rect, rec, final_T, accum, dL_dpix, p8, p1, fl, term, ck, mk, ax);
     return (int)hipGetLastError();
 }
 

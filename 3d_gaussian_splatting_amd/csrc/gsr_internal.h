@@ -111,6 +111,7 @@ constexpr long long kRbMaxCap = 1LL << 30;  // the look-back's 30-bit counts (rb
 // and the binning in use (gsr.h GSR_LAYOUT_*)
 constexpr uint32_t kBufRowBucketed = GSR_LAYOUT_ROW_BUCKETED;
 constexpr uint32_t kBufPresort = GSR_LAYOUT_PRESORT;
+constexpr uint32_t kBufAux = GSR_LAYOUT_AUX, kBufInvDepth = GSR_LAYOUT_INVDEPTH;  // gsr_forward_aux
 // the pre-sort's buffers (GeomLayout: sized from n alone) / the pre-sort itself for an image of
 // gx x gy tiles
 inline bool presort_possible(long long n) { return n >= kPresortMin; }
@@ -200,8 +201,8 @@ __host__ __device__ inline size_t ck_slot_of(bool fixed, uint32_t start, int til
 // `tiles` tiles.  The tile-key sort ping-pongs (kA, vA) <-> (kB, vB); F3 emits into (kA, vA).
 // Then the checkpoint slots: ck_slots x 256 float4, and one live byte per (slot, 16x4 stripe).
 struct BinLayout {
-    size_t kA, vA, kB, vB, hist, rb_hist, ck, ckm, mk = 0, total, ck_slots;
-    BinLayout(long long cap, long long tiles) {
+    size_t kA, vA, kB, vB, hist, rb_hist, ck, ckm, mk = 0, ckz = 0, total, ck_slots;
+    BinLayout(long long cap, long long tiles, bool aux = false) {
         size_t o = 0, n = (size_t)(cap > 0 ? cap : 1);
         auto take = [&](size_t bytes) { size_t r = o; o += align_up(bytes); return r; };
         kA = take(4 * n);
@@ -217,17 +218,20 @@ struct BinLayout {
         // F6's stripe mask of every list entry it loads (one byte each), from which B1 picks the
         // entries it has to visit before loading any record (+ B1's 256-entry window past the end)
         mk = take(n + 64 * GSR_B1_WIN);  // B1 reads whole windows of 64 * GSR_B1_WIN bytes
+        // aux forward (depth / alpha outputs): every checkpoint's fifth value, the depth sum so far
+        // (256 floats per slot, indexed like the slot's float4s), after the plain arrays
+        if (aux) ckz = take(ck_slots * 256 * 4);
         total = o;
     }
 };
 
 struct ImgLayout {
-    size_t ranges, counters, rb_status, done, ovf, ovf2, term, final_T, accum, total;
+    size_t ranges, counters, rb_status, done, ovf, ovf2, term, final_T, accum, accum_z = 0, total;
     static size_t tile_count(int W, int H) {
         const size_t t = (size_t)div_up(W, kTile) * div_up(H, kTile);
         return t ? t : 1;
     }
-    ImgLayout(int W, int H) {
+    ImgLayout(int W, int H, bool aux = false) {
         size_t o = 0;
         auto take = [&](size_t bytes) { size_t r = o; o += align_up(bytes); return r; };
         const size_t tiles = tile_count(W, H);
@@ -242,6 +246,7 @@ struct ImgLayout {
         term = take(4 * tiles * kMaxChunks);  // F6: per tile [termination index, chunk 1..kMaxChunks-1 starts]
         final_T = take(4 * (pix ? pix : 1));
         accum = take(12 * (pix ? pix : 1));  // colour sum without background, 3 x H x W
+        if (aux) accum_z = take(4 * (pix ? pix : 1));  // aux forward: the depth sum, after the plain planes
         total = o;
     }
 };
@@ -253,13 +258,17 @@ struct ImgLayout {
 // the flags are zeroed before B1 (K bytes instead of the 36-B entries), and the gather reads
 // the entries whose flag is set.
 struct PartLayout {
-    size_t p8, p1, fl, total;
-    explicit PartLayout(long long K) {
+    size_t p8, p1, fl, pz = 0, total;
+    explicit PartLayout(long long K, bool aux = false) {
         const size_t n = (size_t)(K > 0 ? K : 1);
         p8 = 0;
         p1 = align_up(32 * n);
         fl = p1 + align_up(4 * n);
         total = fl + align_up(n);
+        if (aux) {  // aux backward: a tenth float per entry (d depth value), after the plain arrays
+            pz = total;
+            total = pz + align_up(4 * n);
+        }
     }
 };
 

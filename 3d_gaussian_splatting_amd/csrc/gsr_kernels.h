@@ -128,6 +128,24 @@ int launch_blend_forward(const gsr_camera& cam, const float bg[3], int ty0, int 
                          float* out_color, float* final_T, float* accum, uint32_t* term, float4* ck, long long cap,
                          hipStream_t s, int vgy = 0, int vh = 0, uint8_t* mk = nullptr);
 
+// F6 with the depth and alpha channels (gsr_forward_aux; full images only): besides the above,
+// out_depth = sum w v and out_alpha = sum w per pixel (v = depth_key[g] as a float, or its
+// reciprocal when inv), the depth sum into accum_z and into every checkpoint's ckz words.  The
+// colour, the chunk table and every other output are the plain launch's, bit for bit.
+int launch_blend_forward_aux(const gsr_camera& cam, const float bg[3], const uint2* ranges,
+                             const uint32_t* sorted_gid, const float4* rec, const uint32_t* depth_key, bool inv,
+                             float* out_color, float* out_depth, float* out_alpha, float* final_T, float* accum,
+                             float* accum_z, uint32_t* term, float4* ck, float* ckz, long long cap, hipStream_t s,
+                             uint8_t* mk);
+// B1 with the depth / alpha gradients (dL_ddepth, dL_dalpha: H x W, nullable = zero): the tenth
+// moment sum w dL/ddepth goes to PartLayout(cap, true).pz; partial: PartLayout(cap, true).
+int launch_blend_backward_aux(const gsr_camera& cam, const float bg[3], const uint2* ranges,
+                              const uint32_t* sorted_gid, const uint4* rect, const float4* rec,
+                              const uint32_t* depth_key, bool inv, const float* final_T, const float* accum,
+                              const float* accum_z, const float* dL_dpix, const float* dL_ddepth,
+                              const float* dL_dalpha, float* partial, long long cap, const uint32_t* term,
+                              const float4* ck, const float* ckz, hipStream_t s, const uint8_t* mk);
+
 // F6 writes term[t] (see kMaxChunks) and the B1 chunk checkpoints `ck` (ImgLayout.ck).
 // B1: per-tile front-to-back gradients -> per-instance partial entry j (PartLayout(cap)), where
 // the emission index j = inst_start[g] + row-major index of the tile in g's band-clipped rect.
@@ -154,7 +172,8 @@ constexpr float kLn2 = 0.6931471805599453f;  // conic A = -2 ln2 a', B = -ln2 b'
 // culled Gaussians).  offsets: the inclusive tile scan in gid order; partial: PartLayout(cap).
 // rrect: the rank-order payload in presort mode (offsets then in rank order), else nullptr
 int launch_gather_grad2d(const uint32_t* offsets, const float* partial, const float4* rec, int W, int H,
-                         long long cap, int P, const uint4* rrect, float* grad2d, hipStream_t s, int split = 1);
+                         long long cap, int P, const uint4* rrect, float* grad2d, hipStream_t s, int split = 1,
+                         bool aux = false);  // aux: partial is PartLayout(cap, true); its pz sums go to slot 9
 
 struct GradOut {
     float *means2D, *conic, *opac, *colors, *means3D, *sh_dc, *sh_rest, *scales, *rots, *cov3D;
@@ -164,7 +183,9 @@ struct GradOut {
 // floats each).  Inputs are indexed by g; grad2d and all outputs by g - g0.
 int launch_preprocess_backward(const gsr_camera& cam, const GaussIn& in, int g0, int g1,
                                const uint32_t* depth_key, const uint32_t* flags, const float* grad2d,
-                               const GradOut& out, hipStream_t s);
+                               const GradOut& out, hipStream_t s, int aux = 0);
+// (aux: 0 = colour only; 1 = grad2d slot 9 is dL/dz of the depth channel, added to the view-space
+// z gradient; 2 = it is dL/d(1/z), scaled by -1/z^2 first)
 // Views mode: B2 of V views in one launch (grid.y = view) from the per-(view, Gaussian) entries
 // v * P + g of depth_key / flags / grad2d; view v's 2D gradients (means2D, conic) go to rows
 // v * P.. of out's, its leaf gradients to `out` (v = 0) or to slice v - 1 of `scratch` (P rows per

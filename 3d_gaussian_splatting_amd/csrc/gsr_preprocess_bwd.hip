@@ -47,15 +47,29 @@ constexpr int kGatherWin = 512;
 
 // rrect (presort mode): index i is a depth rank whose emission range the rank-order offsets give;
 // its Gaussian (record read, grad2d row written) is rrect[i].z.  nullptr: i is the gid itself.
+// AUX (gsr_backward_aux): the entries' tenth moment (pz, sum w dL/ddepth) rides through the same
+// windows and its per-Gaussian sum -- dL/dv of the depth channel -- lands in grad2d slot 9.
+// The aux form is the same kernel with one more trailing argument (the pack PZ = {const float*}, the
+// pz array); with the pack empty the kernel, its arguments included, is the plain one.
+__device__ __forceinline__ const float* gather_pz() { return nullptr; }
+__device__ __forceinline__ const float* gather_pz(const float* p) { return p; }
+template <class... PZ>
 __global__ __launch_bounds__(256) void gather_grad2d_kernel(const uint32_t* __restrict__ offsets,
                                                             const float4* __restrict__ p8,
                                                             const float* __restrict__ p1,
                                                             const uint8_t* __restrict__ fl,
                                                             const float4* __restrict__ rec, float hw, float hh,
                                                             int P, uint32_t cap, const uint4* __restrict__ rrect,
-                                                            float* __restrict__ grad2d, uint32_t split) {
+                                                            float* __restrict__ grad2d, uint32_t split,
+                                                            const PZ... pzp) {
+    constexpr bool AUX = sizeof...(PZ) > 0;
+    static_assert(sizeof...(PZ) <= 1, "one aux argument");
+    static_assert(!AUX || GSR_GATHER_DATA_AHEAD, "the aux gather is written for GSR_GATHER_DATA_AHEAD");
+    const float* __restrict__ pz = gather_pz(pzp...);
     __shared__ float4 w8[2 * kGatherWin];
     __shared__ float w1[kGatherWin];
+    __shared__ float wz[AUX ? kGatherWin : 1];
+    float az = 0.f;
     __shared__ uint32_t wv[kGatherWin / 4];
     const int g0 = blockIdx.x * 256, g = g0 + threadIdx.x;
     const int gl = (P - g0 < 256 ? P - g0 : 256) + g0;  // one past the block's last Gaussian
@@ -88,6 +102,7 @@ __global__ __launch_bounds__(256) void gather_grad2d_kernel(const uint32_t* __re
     };
     float4 d8[4];
     float d1[2];
+    float dz[2] = {0.f, 0.f};
     auto load_data = [&](uint32_t Wx, uint32_t nx, const uint8_t* fb) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -98,6 +113,7 @@ __global__ __launch_bounds__(256) void gather_grad2d_kernel(const uint32_t* __re
         for (int k = 0; k < 2; ++k) {
             const uint32_t i = threadIdx.x + 256u * k;
             d1[k] = i < nx && fb[i] ? p1[(size_t)Wx + i] : 0.f;
+            if constexpr (AUX) dz[k] = i < nx && fb[i] ? pz[(size_t)Wx + i] : 0.f;
         }
     };
     uint32_t fa = 0u, fb2 = 0u;  // flags of the window after the next
@@ -125,6 +141,9 @@ __global__ __launch_bounds__(256) void gather_grad2d_kernel(const uint32_t* __re
         for (int k = 0; k < 2; ++k) {
             const uint32_t i = threadIdx.x + 256u * k;
             if (i < n) w1[i] = d1[k];
+            if constexpr (AUX) {
+                if (i < n) wz[i] = dz[k];
+            }
         }
         uint8_t* const fnx = reinterpret_cast<uint8_t*>(wvd[buf ^ 1]);
         const uint32_t n1 = nwin(W + kGatherWin);
@@ -142,6 +161,7 @@ __global__ __launch_bounds__(256) void gather_grad2d_kernel(const uint32_t* __re
             a[0] += u.x; a[1] += u.y; a[2] += u.z; a[3] += u.w;
             a[4] += v.x; a[5] += v.y; a[6] += v.z; a[7] += v.w;
             a[8] += w1[j - W];
+            if constexpr (AUX) az += wz[j - W];
         }
         __syncthreads();
     }
@@ -194,7 +214,7 @@ __global__ __launch_bounds__(256) void gather_grad2d_kernel(const uint32_t* __re
     float4* dst = reinterpret_cast<float4*>(grad2d + (size_t)kPart * gid);
     dst[0] = make_float4((-A * Sx - B * Sy) * hw, (-C * Sy - B * Sx) * hh, -0.5f * a[2], -a[3]);
     dst[1] = make_float4(-0.5f * a[4], S0 != 0.0f ? S0 / q1.y : 0.0f, a[6], a[7]);
-    dst[2] = make_float4(a[8], 0.f, 0.f, 0.f);
+    dst[2] = make_float4(a[8], AUX ? az : 0.f, 0.f, 0.f);
 }
 
 // Per-Gaussian inputs of B2, loaded before the SH rows are staged so that their HBM
@@ -202,6 +222,7 @@ __global__ __launch_bounds__(256) void gather_grad2d_kernel(const uint32_t* __re
 struct BwdIn {
     bool visible;
     float g2[9];
+    float gz;  // grad2d slot 9: dL/dv of the depth channel (gsr_backward_aux), else 0
     float p0, p1, p2;
     float c3[6];  // cov3D, or (rotation w, x, y, z, unused x2)
     float s[3];   // raw scales
@@ -242,6 +263,7 @@ __device__ __forceinline__ BwdIn load_bwd_in(const GaussIn& in, int g, int o, co
     b.g2[0] = v0.x; b.g2[1] = v0.y; b.g2[2] = v0.z; b.g2[3] = v0.w;
     b.g2[4] = v1.x; b.g2[5] = v1.y; b.g2[6] = v1.z; b.g2[7] = v1.w;
     b.g2[8] = v2.x;
+    b.gz = v2.y;
     b.p0 = in.means3D[3 * g + 0];
     b.p1 = in.means3D[3 * g + 1];
     b.p2 = in.means3D[3 * g + 2];
@@ -262,6 +284,8 @@ __device__ __forceinline__ BwdIn load_bwd_in(const GaussIn& in, int g, int o, co
 
 // One Gaussian's chain rule.  `lrest`: this thread's SH-rest row staged in LDS (read, then
 // overwritten in place with the row's gradient), or nullptr when there is no SH-rest input.
+// AUX: 0 = colour only; 1 = bi.gz is dL/dz of the depth channel; 2 = dL/d(1/z).
+template <int AUX>
 __device__ __forceinline__ void preprocess_backward_one(const gsr_camera& cam, const GaussIn& in, int g, int o,
                                                         const BwdIn& bi, const uint32_t* __restrict__ flags,
                                                         const GradOut& out, float* lrest) {
@@ -508,8 +532,11 @@ __device__ __forceinline__ void preprocess_backward_one(const gsr_camera& cam, c
     }
     const float dtx = xmul * (-fx / tz2) * dJ02;
     const float dty = ymul * (-fy / tz2) * dJ12;
-    const float dtz = (-fx / tz2) * dJ00 + (-fy / tz2) * dJ11 + (2.f * fx * cx / tz3) * dJ02 +
-                      (2.f * fy * cy / tz3) * dJ12;
+    float dtz = (-fx / tz2) * dJ00 + (-fy / tz2) * dJ11 + (2.f * fx * cx / tz3) * dJ02 +
+                (2.f * fy * cy / tz3) * dJ12;
+    // the depth channel blends v = tz (or 1 / tz): its gradient reaches the mean through tz alone
+    if constexpr (AUX == 1) dtz += bi.gz;
+    if constexpr (AUX == 2) dtz += -bi.gz / tz2;
 #pragma unroll
     for (int k = 0; k < 3; ++k) dm[k] += V[4 * k + 0] * dtx + V[4 * k + 1] * dty + V[4 * k + 2] * dtz;
     out.means3D[3 * o + 0] = dm[0];
@@ -573,7 +600,7 @@ __device__ __forceinline__ GradOut view_out(const GradOut& out, const GradOut& s
 }
 
 // SUM: the 2D gradients are the shard's band returns (BandSum), summed here (g0 = 0).
-template <int NV, bool SUM>
+template <int NV, bool SUM, int AUX = 0>
 __global__ __launch_bounds__(256) void preprocess_backward_kernel(
     const CamArg<NV> cams, const GaussIn in, int g0, int n, const uint32_t* __restrict__ depth_key,
     const uint32_t* __restrict__ flags, const float* __restrict__ grad2d, GradOut out, const GradOut scratch,
@@ -623,7 +650,8 @@ __global__ __launch_bounds__(256) void preprocess_backward_kernel(
         }
         __syncthreads();
     }
-    if (o < n) preprocess_backward_one(cam, in, g0 + o, o, bi, flags, out, stage ? sh_lds + threadIdx.x * M3 : nullptr);
+    if (o < n)
+        preprocess_backward_one<AUX>(cam, in, g0 + o, o, bi, flags, out, stage ? sh_lds + threadIdx.x * M3 : nullptr);
     if (stage) {  // coalesced write-back of the SH-rest gradient rows
         __syncthreads();
         const int nf = rows * M3;
@@ -640,26 +668,40 @@ __global__ __launch_bounds__(256) void preprocess_backward_kernel(
 }  // namespace
 
 int launch_gather_grad2d(const uint32_t* offsets, const float* partial, const float4* rec, int W, int H,
-                         long long cap, int P, const uint4* rrect, float* grad2d, hipStream_t s, int split) {
+                         long long cap, int P, const uint4* rrect, float* grad2d, hipStream_t s, int split, bool aux) {
     if (P <= 0) return 0;
-    const PartLayout pl(cap * split);
+    const PartLayout pl(cap * split, aux);
     const char* base = reinterpret_cast<const char*>(partial);
-    hipLaunchKernelGGL(gather_grad2d_kernel, dim3(div_up(P, 256)), dim3(256), 0, s, offsets,
-                       reinterpret_cast<const float4*>(base + pl.p8), reinterpret_cast<const float*>(base + pl.p1),
-                       reinterpret_cast<const uint8_t*>(base + pl.fl), rec, 0.5f * (float)W, 0.5f * (float)H, P,
-                       (uint32_t)cap, rrect, grad2d, (uint32_t)split);
+    if (aux)
+        hipLaunchKernelGGL(gather_grad2d_kernel<const float*>, dim3(div_up(P, 256)), dim3(256), 0, s, offsets,
+                           reinterpret_cast<const float4*>(base + pl.p8), reinterpret_cast<const float*>(base + pl.p1),
+                           reinterpret_cast<const uint8_t*>(base + pl.fl), rec, 0.5f * (float)W, 0.5f * (float)H, P,
+                           (uint32_t)cap, rrect, grad2d, (uint32_t)split,
+                           reinterpret_cast<const float*>(base + pl.pz));
+    else
+        hipLaunchKernelGGL(gather_grad2d_kernel<>, dim3(div_up(P, 256)), dim3(256), 0, s, offsets,
+                           reinterpret_cast<const float4*>(base + pl.p8), reinterpret_cast<const float*>(base + pl.p1),
+                           reinterpret_cast<const uint8_t*>(base + pl.fl), rec, 0.5f * (float)W, 0.5f * (float)H, P,
+                           (uint32_t)cap, rrect, grad2d, (uint32_t)split);
     return (int)hipGetLastError();
 }
 
 int launch_preprocess_backward(const gsr_camera& cam, const GaussIn& in, int g0, int g1,
                                const uint32_t* depth_key, const uint32_t* flags, const float* grad2d,
-                               const GradOut& out, hipStream_t s) {
+                               const GradOut& out, hipStream_t s, int aux) {
     const int n = g1 - g0;
     if (n <= 0) return 0;
     const size_t lds = (in.sh_rest && !in.colors) ? sizeof(float) * 256 * 3 * in.M_rest : 0;
     const CamArg<1> c1{{cam}};
-    hipLaunchKernelGGL((preprocess_backward_kernel<1, false>), dim3(div_up(n, 256)), dim3(256), lds, s, c1, in, g0,
-                       n, depth_key, flags, grad2d, out, GradOut{}, BandSum{});
+    if (aux == 1)
+        hipLaunchKernelGGL((preprocess_backward_kernel<1, false, 1>), dim3(div_up(n, 256)), dim3(256), lds, s, c1, in,
+                           g0, n, depth_key, flags, grad2d, out, GradOut{}, BandSum{});
+    else if (aux == 2)
+        hipLaunchKernelGGL((preprocess_backward_kernel<1, false, 2>), dim3(div_up(n, 256)), dim3(256), lds, s, c1, in,
+                           g0, n, depth_key, flags, grad2d, out, GradOut{}, BandSum{});
+    else
+        hipLaunchKernelGGL((preprocess_backward_kernel<1, false>), dim3(div_up(n, 256)), dim3(256), lds, s, c1, in, g0,
+                           n, depth_key, flags, grad2d, out, GradOut{}, BandSum{});
     return (int)hipGetLastError();
 }
 

@@ -65,6 +65,8 @@ struct RenderOutput {
     torch::Tensor num_rendered_device;  // (1,) int32 on the device: K (no host wait to get it)
     int num_rendered = -1;              // K when the forward read it back (max_rendered == 0), else -1
     int capacity = 0;                   // instances the forward's binning held
+    torch::Tensor depth;              // (H,W) sum w z (sum w / z: inverse depth); defined iff asked for
+    torch::Tensor alpha;              // (H,W) sum w = 1 - final T;                defined iff asked for
 };
 
 // K of a render, read back now (waits for the render's stream): gsr_read_num_rendered's
@@ -126,6 +128,16 @@ std::vector<torch::Tensor> rasterize_gaussians(
     const torch::Tensor& colors_precomp, const torch::Tensor& opacities, const torch::Tensor& scales,
     const torch::Tensor& rotations, const torch::Tensor& cov3D_precomp);
 
+// The same with the depth and alpha outputs (gsr.h gsr_forward_aux): returns {color, depth (H,W),
+// alpha (H,W), radii, K, {host K or -1, capacity}}; color, depth and alpha are differentiable.
+// depth = sum w z over the blended pairs (sum w / z with inverse_depth), alpha = sum w; both
+// un-normalised, without background.  Full images only.
+std::vector<torch::Tensor> rasterize_gaussians_aux(
+    const RasterCamera& cam, const RasterSettings& rs, bool inverse_depth, const torch::Tensor& means3D,
+    const torch::Tensor& means2D, const torch::Tensor& sh_dc, const torch::Tensor& sh_rest,
+    const torch::Tensor& colors_precomp, const torch::Tensor& opacities, const torch::Tensor& scales,
+    const torch::Tensor& rotations, const torch::Tensor& cov3D_precomp);
+
 // torch-op SH evaluation (PipelineParams::convert_SHs_python_ path): colours for
 // directions (P,3) and coefficients (P,M,3) at degree D; +0.5 and clamp at 0 as in-kernel.
 torch::Tensor eval_sh_colors(int D, const torch::Tensor& sh, const torch::Tensor& dirs);
@@ -133,7 +145,7 @@ torch::Tensor eval_sh_colors(int D, const torch::Tensor& sh, const torch::Tensor
 template <class Model, class Pipe>
 RenderOutput render(const RasterCamera& cam, Model& pc, const Pipe& pipe, const std::array<float, 3>& bg,
                     float scaling_modifier = 1.f, std::optional<torch::Tensor> override_color = std::nullopt,
-                    BinningCapacity* binning = nullptr) {
+                    BinningCapacity* binning = nullptr, bool return_depth = false, bool inverse_depth = false) {
     const auto& xyz = pc.get_xyz();
     auto screenspace = torch::zeros_like(xyz).requires_grad_(true);
     RasterSettings rs;
@@ -167,11 +179,25 @@ RenderOutput render(const RasterCamera& cam, Model& pc, const Pipe& pipe, const 
         sh_dc = core.features_dc_;
         sh_rest = core.features_rest_;
     }
-    std::vector<torch::Tensor> outs = rasterize_gaussians(cam, rs, xyz, screenspace, sh_dc, sh_rest, colors, pc.get_opacity(),
-                                    scales, rotations, cov3D);
+    // return_depth: one pass renders colour, depth and alpha (o.depth / o.alpha, differentiable);
+    // without it the colour-only Function and kernels run, as before
+    std::vector<torch::Tensor> outs;
+    torch::Tensor depth, alpha;
+    if (return_depth) {
+        auto a = rasterize_gaussians_aux(cam, rs, inverse_depth, xyz, screenspace, sh_dc, sh_rest, colors,
+                                         pc.get_opacity(), scales, rotations, cov3D);
+        depth = a[1];
+        alpha = a[2];
+        outs = {a[0], a[3], a[4], a[5]};
+    } else {
+        outs = rasterize_gaussians(cam, rs, xyz, screenspace, sh_dc, sh_rest, colors, pc.get_opacity(), scales,
+                                   rotations, cov3D);
+    }
     RenderOutput o{outs[0], screenspace, outs[1] > 0, outs[1], outs[2]};
     o.num_rendered = outs[3][0].item<int32_t>();  // host tensor: no device wait
     o.capacity = outs[3][1].item<int32_t>();
+    o.depth = depth;
+    o.alpha = alpha;
     if (binning) binning->observe(o);
     return o;
 }
@@ -182,8 +208,9 @@ RenderOutput render(const RasterCamera& cam, Model& pc, const Pipe& pipe, const 
 template <class Model, class Pipe>
 RenderOutput render(const RasterCamera& cam, Model& pc, const Pipe& pipe, const torch::Tensor& bg,
                     float scaling_modifier = 1.f, std::optional<torch::Tensor> override_color = std::nullopt,
-                    BinningCapacity* binning = nullptr) {
-    return render(cam, pc, pipe, background(bg), scaling_modifier, std::move(override_color), binning);
+                    BinningCapacity* binning = nullptr, bool return_depth = false, bool inverse_depth = false) {
+    return render(cam, pc, pipe, background(bg), scaling_modifier, std::move(override_color), binning, return_depth,
+                  inverse_depth);
 }
 
 namespace detail {
@@ -191,6 +218,7 @@ namespace detail {
 // gsr_trainer.h): torch owns every scratch byte; `Frame` keeps them from forward to backward.
 struct Frame {
     torch::Tensor color, radii, geom, binning, image;
+    torch::Tensor depth, alpha;  // the aux forward's outputs (undefined otherwise)
     gsr_buffers bufs{};
     gsr_camera cam{};
     gsr_raster_settings settings{};

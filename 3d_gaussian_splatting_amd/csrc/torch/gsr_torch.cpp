@@ -108,7 +108,7 @@ FwdResult forward_impl(const RasterCamera& cam, const RasterSettings& rs, const 
                        const torch::Tensor& sh_dc, const torch::Tensor& sh_rest,
                        const torch::Tensor& colors, const torch::Tensor& opac,
                        const torch::Tensor& scales, const torch::Tensor& rots,
-                       const torch::Tensor& cov3D) {
+                       const torch::Tensor& cov3D, bool aux = false, bool inverse_depth = false) {
     TORCH_CHECK(means3D.dim() == 2 && means3D.size(1) == 3, "means3D must be (P,3)");
     const int64_t P = means3D.size(0);
     auto dev = means3D.device();
@@ -118,16 +118,26 @@ FwdResult forward_impl(const RasterCamera& cam, const RasterSettings& rs, const 
     r.radii = torch::empty({P}, fopt.dtype(torch::kInt32));
     const gsr_camera c = cam.to_c();
     const gsr_gaussians g = make_gaussians(rs, means3D, sh_dc, sh_rest, colors, opac, scales, rots, cov3D);
-    const gsr_raster_settings s = make_settings(rs);
+    gsr_raster_settings s = make_settings(rs);
     AllocCtx geom{dev, {}}, bin{dev, {}}, img{dev, {}};
     gsr_buffers b{};
     AllocCtx* ctxs[3] = {&geom, &bin, &img};  // one context per role
-    check(gsr_forward(&c, &g, &s, r.color.data_ptr<float>(), P ? r.radii.data_ptr<int32_t>() : nullptr,
-                      [](void* ctx, size_t n) { return alloc_cb(static_cast<AllocCtx**>(ctx)[0], n); },
-                      [](void* ctx, size_t n) { return alloc_cb(static_cast<AllocCtx**>(ctx)[1], n); },
-                      [](void* ctx, size_t n) { return alloc_cb(static_cast<AllocCtx**>(ctx)[2], n); },
-                      (void*)ctxs, &b, cur_stream()),
-          "gsr_forward");
+    const gsr_alloc_fn a0 = [](void* ctx, size_t n) { return alloc_cb(static_cast<AllocCtx**>(ctx)[0], n); };
+    const gsr_alloc_fn a1 = [](void* ctx, size_t n) { return alloc_cb(static_cast<AllocCtx**>(ctx)[1], n); };
+    const gsr_alloc_fn a2 = [](void* ctx, size_t n) { return alloc_cb(static_cast<AllocCtx**>(ctx)[2], n); };
+    int32_t* const rad = P ? r.radii.data_ptr<int32_t>() : nullptr;
+    if (aux) {  // the depth / alpha channels ride along (gsr.h gsr_forward_aux)
+        r.depth = torch::empty({cam.height, cam.width}, fopt);
+        r.alpha = torch::empty({cam.height, cam.width}, fopt);
+        s.flags |= GSR_FLAG_AUX | (inverse_depth ? GSR_FLAG_INVDEPTH : 0u);
+        const gsr_aux_out ao{r.depth.data_ptr<float>(), r.alpha.data_ptr<float>()};
+        check(gsr_forward_aux(&c, &g, &s, r.color.data_ptr<float>(), rad, a0, a1, a2, (void*)ctxs, &b, cur_stream(),
+                              &ao),
+              "gsr_forward_aux");
+    } else {
+        check(gsr_forward(&c, &g, &s, r.color.data_ptr<float>(), rad, a0, a1, a2, (void*)ctxs, &b, cur_stream()),
+              "gsr_forward");
+    }
     r.geom = geom.keep.at(0);
     r.binning = bin.keep.empty() ? torch::Tensor() : bin.keep.at(0);
     r.image = img.keep.at(0);
@@ -153,34 +163,113 @@ gsr_buffers buffers_of(const torch::Tensor& geom, const torch::Tensor& binning, 
 using torch::autograd::AutogradContext;
 using torch::autograd::variable_list;
 
+// What both autograd Functions keep from forward to backward, and how backward gets it back.
+void save_frame(AutogradContext* ctx, const RasterCamera& cam, const RasterSettings& rs, const FwdResult& r,
+                const torch::Tensor& means2D) {
+    ctx->saved_data["has_m2d"] = present(means2D);
+    ctx->saved_data["K"] = (int64_t)r.bufs.num_rendered;
+    ctx->saved_data["cap"] = (int64_t)r.bufs.capacity;
+    ctx->saved_data["n_local"] = (int64_t)r.bufs.n_local;
+    ctx->saved_data["layout"] = (int64_t)r.bufs.layout;
+    ctx->saved_data["cam_w"] = (int64_t)cam.width;
+    ctx->saved_data["cam_h"] = (int64_t)cam.height;
+    ctx->saved_data["cam_tx"] = (double)cam.tanfovx;
+    ctx->saved_data["cam_ty"] = (double)cam.tanfovy;
+    ctx->saved_data["cam_v"] = std::vector<double>(cam.viewmatrix.begin(), cam.viewmatrix.end());
+    ctx->saved_data["cam_p"] = std::vector<double>(cam.projmatrix.begin(), cam.projmatrix.end());
+    ctx->saved_data["cam_c"] = std::vector<double>(cam.campos.begin(), cam.campos.end());
+    ctx->saved_data["bg"] = std::vector<double>(rs.bg.begin(), rs.bg.end());
+    ctx->saved_data["smod"] = (double)rs.scale_modifier;
+    ctx->saved_data["D"] = (int64_t)rs.sh_degree;
+    ctx->saved_data["ty0"] = (int64_t)rs.tile_y0;
+    ctx->saved_data["ty1"] = (int64_t)rs.tile_y1;
+    ctx->saved_data["debug"] = rs.debug;
+    ctx->saved_data["max_rendered"] = (int64_t)rs.max_rendered;
+}
+
+struct SavedFrame {
+    RasterCamera cam;
+    RasterSettings rs;
+    int32_t K, cap, n_local;
+    uint32_t layout;
+};
+
+SavedFrame restore_frame(AutogradContext* ctx) {
+    SavedFrame f;
+    RasterCamera& cam = f.cam;
+    cam.width = (int)ctx->saved_data["cam_w"].toInt();
+    cam.height = (int)ctx->saved_data["cam_h"].toInt();
+    cam.tanfovx = (float)ctx->saved_data["cam_tx"].toDouble();
+    cam.tanfovy = (float)ctx->saved_data["cam_ty"].toDouble();
+    auto V = ctx->saved_data["cam_v"].toDoubleVector();
+    auto Pm = ctx->saved_data["cam_p"].toDoubleVector();
+    auto C = ctx->saved_data["cam_c"].toDoubleVector();
+    for (int i = 0; i < 16; ++i) cam.viewmatrix[i] = (float)V[i], cam.projmatrix[i] = (float)Pm[i];
+    for (int i = 0; i < 3; ++i) cam.campos[i] = (float)C[i];
+    RasterSettings& rs = f.rs;
+    auto bg = ctx->saved_data["bg"].toDoubleVector();
+    for (int i = 0; i < 3; ++i) rs.bg[i] = (float)bg[i];
+    rs.scale_modifier = (float)ctx->saved_data["smod"].toDouble();
+    rs.sh_degree = (int)ctx->saved_data["D"].toInt();
+    rs.tile_y0 = (int)ctx->saved_data["ty0"].toInt();
+    rs.tile_y1 = (int)ctx->saved_data["ty1"].toInt();
+    rs.debug = ctx->saved_data["debug"].toBool();
+    rs.max_rendered = (int)ctx->saved_data["max_rendered"].toInt();
+    f.K = (int32_t)ctx->saved_data["K"].toInt();
+    f.cap = (int32_t)ctx->saved_data["cap"].toInt();
+    f.n_local = (int32_t)ctx->saved_data["n_local"].toInt();
+    f.layout = (uint32_t)ctx->saved_data["layout"].toInt();
+    return f;
+}
+
+// The leaf gradient tensors of one backward and the gsr_grads pointing at them.
+struct LeafGrads {
+    torch::Tensor means2D, opac, means3D, dc, rest, colors, scales, rots, cov;
+    gsr_grads gg{};
+    LeafGrads(const torch::Tensor& means3D_in, const torch::Tensor& sh_dc, const torch::Tensor& sh_rest,
+              const torch::Tensor& colors_in, const torch::Tensor& opac_in, const torch::Tensor& scales_in,
+              const torch::Tensor& rots_in, const torch::Tensor& cov3D) {
+        const int64_t P = means3D_in.size(0);
+        auto fo = means3D_in.options();
+        means2D = torch::empty({P, 3}, fo);
+        opac = torch::empty_like(opac_in);
+        means3D = torch::empty({P, 3}, fo);
+        gg.dL_dmeans2D = means2D.data_ptr<float>();
+        gg.dL_dopacity = opac.data_ptr<float>();
+        gg.dL_dmeans3D = means3D.data_ptr<float>();
+        if (present(colors_in)) {
+            colors = torch::empty_like(colors_in);
+            gg.dL_dcolors = colors.data_ptr<float>();
+        } else {
+            dc = torch::empty_like(sh_dc);
+            gg.dL_dsh_dc = dc.data_ptr<float>();
+            if (present(sh_rest)) {
+                rest = torch::empty_like(sh_rest);
+                gg.dL_dsh_rest = rest.data_ptr<float>();
+            }
+        }
+        if (present(cov3D)) {
+            cov = torch::empty_like(cov3D);
+            gg.dL_dcov3D = cov.data_ptr<float>();
+        } else {
+            scales = torch::empty_like(scales_in);
+            rots = torch::empty_like(rots_in);
+            gg.dL_dscales = scales.data_ptr<float>();
+            gg.dL_drotations = rots.data_ptr<float>();
+        }
+    }
+};
+
 class RasterizeGaussians : public torch::autograd::Function<RasterizeGaussians> {
    public:
     static variable_list forward(AutogradContext* ctx, const RasterCamera& cam, const RasterSettings& rs,
                                  torch::Tensor means3D, torch::Tensor means2D, torch::Tensor sh_dc,
                                  torch::Tensor sh_rest, torch::Tensor colors, torch::Tensor opac,
                                  torch::Tensor scales, torch::Tensor rots, torch::Tensor cov3D) {
-        ctx->saved_data["has_m2d"] = present(means2D);
         auto r = forward_impl(cam, rs, means3D, sh_dc, sh_rest, colors, opac, scales, rots, cov3D);
         ctx->save_for_backward({means3D, sh_dc, sh_rest, colors, opac, scales, rots, cov3D, r.geom, r.binning,
                                 r.image});
-        ctx->saved_data["K"] = (int64_t)r.bufs.num_rendered;
-        ctx->saved_data["cap"] = (int64_t)r.bufs.capacity;
-        ctx->saved_data["n_local"] = (int64_t)r.bufs.n_local;
-        ctx->saved_data["layout"] = (int64_t)r.bufs.layout;
-        ctx->saved_data["cam_w"] = (int64_t)cam.width;
-        ctx->saved_data["cam_h"] = (int64_t)cam.height;
-        ctx->saved_data["cam_tx"] = (double)cam.tanfovx;
-        ctx->saved_data["cam_ty"] = (double)cam.tanfovy;
-        ctx->saved_data["cam_v"] = std::vector<double>(cam.viewmatrix.begin(), cam.viewmatrix.end());
-        ctx->saved_data["cam_p"] = std::vector<double>(cam.projmatrix.begin(), cam.projmatrix.end());
-        ctx->saved_data["cam_c"] = std::vector<double>(cam.campos.begin(), cam.campos.end());
-        ctx->saved_data["bg"] = std::vector<double>(rs.bg.begin(), rs.bg.end());
-        ctx->saved_data["smod"] = (double)rs.scale_modifier;
-        ctx->saved_data["D"] = (int64_t)rs.sh_degree;
-        ctx->saved_data["ty0"] = (int64_t)rs.tile_y0;
-        ctx->saved_data["ty1"] = (int64_t)rs.tile_y1;
-        ctx->saved_data["debug"] = rs.debug;
-        ctx->saved_data["max_rendered"] = (int64_t)rs.max_rendered;
+        save_frame(ctx, cam, rs, r, means2D);
         auto kdev = r.k_device();
         auto kinfo = torch::tensor({r.bufs.num_rendered, r.bufs.capacity}, torch::kInt32);
         ctx->mark_non_differentiable({r.radii, kdev, kinfo});
@@ -191,71 +280,71 @@ class RasterizeGaussians : public torch::autograd::Function<RasterizeGaussians> 
         auto sv = ctx->get_saved_variables();
         auto means3D = sv[0], sh_dc = sv[1], sh_rest = sv[2], colors = sv[3], opac = sv[4], scales = sv[5],
              rots = sv[6], cov3D = sv[7], geom = sv[8], binning = sv[9], image = sv[10];
-        RasterCamera cam;
-        cam.width = (int)ctx->saved_data["cam_w"].toInt();
-        cam.height = (int)ctx->saved_data["cam_h"].toInt();
-        cam.tanfovx = (float)ctx->saved_data["cam_tx"].toDouble();
-        cam.tanfovy = (float)ctx->saved_data["cam_ty"].toDouble();
-        auto V = ctx->saved_data["cam_v"].toDoubleVector();
-        auto Pm = ctx->saved_data["cam_p"].toDoubleVector();
-        auto C = ctx->saved_data["cam_c"].toDoubleVector();
-        for (int i = 0; i < 16; ++i) cam.viewmatrix[i] = (float)V[i], cam.projmatrix[i] = (float)Pm[i];
-        for (int i = 0; i < 3; ++i) cam.campos[i] = (float)C[i];
-        RasterSettings rs;
-        auto bg = ctx->saved_data["bg"].toDoubleVector();
-        for (int i = 0; i < 3; ++i) rs.bg[i] = (float)bg[i];
-        rs.scale_modifier = (float)ctx->saved_data["smod"].toDouble();
-        rs.sh_degree = (int)ctx->saved_data["D"].toInt();
-        rs.tile_y0 = (int)ctx->saved_data["ty0"].toInt();
-        rs.tile_y1 = (int)ctx->saved_data["ty1"].toInt();
-        rs.debug = ctx->saved_data["debug"].toBool();
-        rs.max_rendered = (int)ctx->saved_data["max_rendered"].toInt();
-        const int32_t K = (int32_t)ctx->saved_data["K"].toInt();
-        const int32_t cap = (int32_t)ctx->saved_data["cap"].toInt();
-        const int32_t n_local = (int32_t)ctx->saved_data["n_local"].toInt();
-        const uint32_t layout = (uint32_t)ctx->saved_data["layout"].toInt();
+        const SavedFrame f = restore_frame(ctx);
         auto dL_dcolor = grad_out[0].contiguous();
-        const int64_t P = means3D.size(0);
-        auto fo = means3D.options();
-        auto g_means2D = torch::empty({P, 3}, fo);
-        auto g_opac = torch::empty_like(opac);
-        auto g_means3D = torch::empty({P, 3}, fo);
-        torch::Tensor g_dc, g_rest, g_colors, g_scales, g_rots, g_cov;
-        gsr_grads gg{};
-        gg.dL_dmeans2D = g_means2D.data_ptr<float>();
-        gg.dL_dopacity = g_opac.data_ptr<float>();
-        gg.dL_dmeans3D = g_means3D.data_ptr<float>();
-        if (present(colors)) {
-            g_colors = torch::empty_like(colors);
-            gg.dL_dcolors = g_colors.data_ptr<float>();
-        } else {
-            g_dc = torch::empty_like(sh_dc);
-            gg.dL_dsh_dc = g_dc.data_ptr<float>();
-            if (present(sh_rest)) {
-                g_rest = torch::empty_like(sh_rest);
-                gg.dL_dsh_rest = g_rest.data_ptr<float>();
-            }
-        }
-        if (present(cov3D)) {
-            g_cov = torch::empty_like(cov3D);
-            gg.dL_dcov3D = g_cov.data_ptr<float>();
-        } else {
-            g_scales = torch::empty_like(scales);
-            g_rots = torch::empty_like(rots);
-            gg.dL_dscales = g_scales.data_ptr<float>();
-            gg.dL_drotations = g_rots.data_ptr<float>();
-        }
-        const gsr_camera c = cam.to_c();
-        const gsr_gaussians g = make_gaussians(rs, means3D, sh_dc, sh_rest, colors, opac, scales, rots, cov3D);
-        const gsr_raster_settings s = make_settings(rs);
-        const gsr_buffers b = buffers_of(geom, binning, image, K, cap, n_local, layout);
+        LeafGrads lg(means3D, sh_dc, sh_rest, colors, opac, scales, rots, cov3D);
+        const gsr_camera c = f.cam.to_c();
+        const gsr_gaussians g = make_gaussians(f.rs, means3D, sh_dc, sh_rest, colors, opac, scales, rots, cov3D);
+        const gsr_raster_settings s = make_settings(f.rs);
+        const gsr_buffers b = buffers_of(geom, binning, image, f.K, f.cap, f.n_local, f.layout);
         AllocCtx scratch{means3D.device(), {}};
-        check(gsr_backward(&c, &g, &s, &b, dL_dcolor.data_ptr<float>(), alloc_cb, &scratch, &gg, cur_stream()),
+        check(gsr_backward(&c, &g, &s, &b, dL_dcolor.data_ptr<float>(), alloc_cb, &scratch, &lg.gg, cur_stream()),
               "gsr_backward");
         // inputs of forward(): cam, rs, means3D, means2D, sh_dc, sh_rest, colors, opac, scales, rots, cov3D
-        if (!ctx->saved_data["has_m2d"].toBool()) g_means2D = torch::Tensor();
-        return {torch::Tensor(), torch::Tensor(), g_means3D, g_means2D, g_dc, g_rest, g_colors, g_opac,
-                g_scales, g_rots, g_cov};
+        if (!ctx->saved_data["has_m2d"].toBool()) lg.means2D = torch::Tensor();
+        return {torch::Tensor(), torch::Tensor(), lg.means3D, lg.means2D, lg.dc, lg.rest, lg.colors, lg.opac,
+                lg.scales, lg.rots, lg.cov};
+    }
+};
+
+// RasterizeGaussians with the depth and alpha outputs (gsr_forward_aux / gsr_backward_aux): one
+// forward, one backward for a loss over colour, depth and alpha.  An output the loss does not use
+// arrives as an undefined gradient and travels as NULL (= zero).
+class RasterizeGaussiansAux : public torch::autograd::Function<RasterizeGaussiansAux> {
+   public:
+    static variable_list forward(AutogradContext* ctx, const RasterCamera& cam, const RasterSettings& rs,
+                                 bool inverse_depth, torch::Tensor means3D, torch::Tensor means2D,
+                                 torch::Tensor sh_dc, torch::Tensor sh_rest, torch::Tensor colors, torch::Tensor opac,
+                                 torch::Tensor scales, torch::Tensor rots, torch::Tensor cov3D) {
+        auto r = forward_impl(cam, rs, means3D, sh_dc, sh_rest, colors, opac, scales, rots, cov3D, true,
+                              inverse_depth);
+        ctx->save_for_backward({means3D, sh_dc, sh_rest, colors, opac, scales, rots, cov3D, r.geom, r.binning,
+                                r.image});
+        save_frame(ctx, cam, rs, r, means2D);
+        ctx->saved_data["inverse_depth"] = inverse_depth;
+        auto kdev = r.k_device();
+        auto kinfo = torch::tensor({r.bufs.num_rendered, r.bufs.capacity}, torch::kInt32);
+        ctx->mark_non_differentiable({r.radii, kdev, kinfo});
+        return {r.color, r.depth, r.alpha, r.radii, kdev, kinfo};
+    }
+
+    static variable_list backward(AutogradContext* ctx, variable_list grad_out) {
+        auto sv = ctx->get_saved_variables();
+        auto means3D = sv[0], sh_dc = sv[1], sh_rest = sv[2], colors = sv[3], opac = sv[4], scales = sv[5],
+             rots = sv[6], cov3D = sv[7], geom = sv[8], binning = sv[9], image = sv[10];
+        const SavedFrame f = restore_frame(ctx);
+        auto dL_dcolor = grad_out[0].defined()
+                             ? grad_out[0].contiguous()
+                             : torch::zeros({3, f.cam.height, f.cam.width}, means3D.options());
+        torch::Tensor dL_ddepth, dL_dalpha;
+        if (grad_out[1].defined()) dL_ddepth = grad_out[1].contiguous();
+        if (grad_out[2].defined()) dL_dalpha = grad_out[2].contiguous();
+        LeafGrads lg(means3D, sh_dc, sh_rest, colors, opac, scales, rots, cov3D);
+        const gsr_camera c = f.cam.to_c();
+        const gsr_gaussians g = make_gaussians(f.rs, means3D, sh_dc, sh_rest, colors, opac, scales, rots, cov3D);
+        gsr_raster_settings s = make_settings(f.rs);
+        s.flags |= GSR_FLAG_AUX | (ctx->saved_data["inverse_depth"].toBool() ? GSR_FLAG_INVDEPTH : 0u);
+        const gsr_buffers b = buffers_of(geom, binning, image, f.K, f.cap, f.n_local, f.layout);
+        const gsr_aux_grads ag{dL_ddepth.defined() ? dL_ddepth.data_ptr<float>() : nullptr,
+                               dL_dalpha.defined() ? dL_dalpha.data_ptr<float>() : nullptr};
+        AllocCtx scratch{means3D.device(), {}};
+        check(gsr_backward_aux(&c, &g, &s, &b, dL_dcolor.data_ptr<float>(), alloc_cb, &scratch, &lg.gg, cur_stream(),
+                               &ag),
+              "gsr_backward_aux");
+        // inputs of forward(): cam, rs, inverse_depth, means3D, means2D, sh_dc, sh_rest, colors, opac, scales, ...
+        if (!ctx->saved_data["has_m2d"].toBool()) lg.means2D = torch::Tensor();
+        return {torch::Tensor(), torch::Tensor(), torch::Tensor(), lg.means3D, lg.means2D, lg.dc, lg.rest, lg.colors,
+                lg.opac, lg.scales, lg.rots, lg.cov};
     }
 };
 
@@ -424,6 +513,19 @@ std::vector<torch::Tensor> rasterize_gaussians(const RasterCamera& cam, const Ra
                                      opt_in(colors), opac, opt_in(scales), opt_in(rots), opt_in(cov3D));
 }
 
+std::vector<torch::Tensor> rasterize_gaussians_aux(const RasterCamera& cam, const RasterSettings& rs,
+                                                   bool inverse_depth, const torch::Tensor& means3D,
+                                                   const torch::Tensor& means2D, const torch::Tensor& sh_dc,
+                                                   const torch::Tensor& sh_rest, const torch::Tensor& colors,
+                                                   const torch::Tensor& opac, const torch::Tensor& scales,
+                                                   const torch::Tensor& rots, const torch::Tensor& cov3D) {
+    auto none = torch::empty({0}, means3D.options());
+    auto opt_in = [&](const torch::Tensor& t) { return t.defined() ? t : none; };
+    return RasterizeGaussiansAux::apply(cam, rs, inverse_depth, means3D, opt_in(means2D), opt_in(sh_dc),
+                                        opt_in(sh_rest), opt_in(colors), opac, opt_in(scales), opt_in(rots),
+                                        opt_in(cov3D));
+}
+
 torch::Tensor eval_sh_colors(int D, const torch::Tensor& sh, const torch::Tensor& dirs) {
     // same basis and constants as the kernels
     const double C0 = 0.28209479177387814, C1 = 0.4886025119029199;
@@ -521,6 +623,19 @@ PYBIND11_MODULE(_gsr_torch, m) {
         },
         py::arg("cam"), py::arg("settings"), py::arg("means3D"), py::arg("means2D"), py::arg("sh_dc"),
         py::arg("sh_rest"), py::arg("colors_precomp"), py::arg("opacities"), py::arg("scales"),
+        py::arg("rotations"), py::arg("cov3D_precomp"));
+    m.def(
+        "rasterize_gaussians_aux",
+        [](const gsr::RasterCamera& cam, const gsr::RasterSettings& rs, bool inverse_depth, torch::Tensor means3D,
+           torch::Tensor means2D, c10::optional<torch::Tensor> sh_dc, c10::optional<torch::Tensor> sh_rest,
+           c10::optional<torch::Tensor> colors, torch::Tensor opac, c10::optional<torch::Tensor> scales,
+           c10::optional<torch::Tensor> rots, c10::optional<torch::Tensor> cov3D) {
+            auto r = gsr::rasterize_gaussians_aux(cam, rs, inverse_depth, means3D, means2D, opt(sh_dc), opt(sh_rest),
+                                                  opt(colors), opac, opt(scales), opt(rots), opt(cov3D));
+            return py::make_tuple(r[0], r[1], r[2], r[3]);
+        },
+        py::arg("cam"), py::arg("settings"), py::arg("inverse_depth"), py::arg("means3D"), py::arg("means2D"),
+        py::arg("sh_dc"), py::arg("sh_rest"), py::arg("colors_precomp"), py::arg("opacities"), py::arg("scales"),
         py::arg("rotations"), py::arg("cov3D_precomp"));
     m.def("eval_sh_colors", &gsr::eval_sh_colors);
     m.def(

@@ -23,6 +23,11 @@ HIP_LIB = os.environ.get("GSR_HIP_LIB") or os.path.join(LIB_DIR, "libgsr_hip.so"
 ABI_VERSION = 4
 GSR_FLAG_DEBUG = 1
 GSR_FLAG_ROW_SPANS = 2  # gsr.h: gsr_shard_forward row_hist = 3 x grid_y (instances, rect start rows, end rows)
+GSR_FLAG_AUX = 4        # gsr.h: implied by gsr_forward_aux / gsr_backward_aux
+GSR_FLAG_INVDEPTH = 8   # gsr.h: the aux depth channel blends 1 / z
+GSR_LAYOUT_AUX = 4      # gsr_buffers.layout bits written by gsr_forward_aux
+GSR_LAYOUT_INVDEPTH = 8
+GSR_ERR_LAYOUT = -13
 GSR_ERR_OVERFLOW = -4
 GSR_GRAD2D_STRIDE = 12
 GSR_MAX_BATCH = 64
@@ -44,7 +49,8 @@ EXPORTS = ["gsr_abi_version", "gsr_last_error", "gsr_forward", "gsr_read_num_ren
            "gsr_band_forward", "gsr_band_backward", "gsr_shard_backward", "gsr_exchange_block_bytes",
            "gsr_shard_state_bytes", "gsr_view", "gsr_geom_bytes", "gsr_binning_bytes",
            "gsr_image_bytes", "gsr_scratch_bytes", "gsr_ck_pool_slots", "gsr_profile_enable", "gsr_profile_read",
-           "gsr_stage_name", "gsr_band_publish", "gsr_gather_finish"]
+           "gsr_stage_name", "gsr_band_publish", "gsr_gather_finish", "gsr_forward_aux", "gsr_backward_aux",
+           "gsr_binning_bytes_aux", "gsr_image_bytes_aux", "gsr_scratch_bytes_aux"]
 # include/gsr/gsr_train.h (training-step kernels)
 TRAIN_EXPORTS = ["gsr_activate", "gsr_loss_scratch_bytes", "gsr_loss_forward", "gsr_loss_backward", "gsr_adam_step",
                  "gsr_adam_step_guarded", "gsr_densify_stats", "gsr_densify_stats_guarded", "gsr_compact_scratch_bytes", "gsr_compact_index", "gsr_gather_rows",
@@ -88,6 +94,14 @@ class Buffers(ctypes.Structure):
     _fields_ = [("geom", ctypes.c_void_p), ("binning", ctypes.c_void_p), ("image", ctypes.c_void_p),
                 ("num_rendered", ctypes.c_int32), ("capacity", ctypes.c_int32), ("n_local", ctypes.c_int32),
                 ("layout", ctypes.c_uint32)]
+
+
+class AuxOut(ctypes.Structure):
+    _fields_ = [("depth", ctypes.c_void_p), ("alpha", ctypes.c_void_p)]
+
+
+class AuxGrads(ctypes.Structure):
+    _fields_ = [("dL_ddepth", ctypes.c_void_p), ("dL_dalpha", ctypes.c_void_p)]
 
 
 class AdamGroup(ctypes.Structure):
@@ -141,6 +155,11 @@ def load_hip() -> ctypes.CDLL:
         L.gsr_backward.restype = ctypes.c_int
         L.gsr_backward.argtypes = [ctypes.POINTER(Camera), ctypes.POINTER(Gaussians), ctypes.POINTER(Settings),
                                    ctypes.POINTER(Buffers), vp, ALLOC_FN, vp, ctypes.POINTER(Grads), vp]
+        # depth / alpha outputs: the plain calls' arguments plus the aux struct
+        L.gsr_forward_aux.restype = ctypes.c_int
+        L.gsr_forward_aux.argtypes = list(L.gsr_forward.argtypes) + [ctypes.POINTER(AuxOut)]
+        L.gsr_backward_aux.restype = ctypes.c_int
+        L.gsr_backward_aux.argtypes = list(L.gsr_backward.argtypes) + [ctypes.POINTER(AuxGrads)]
         L.gsr_backward_blend.restype = ctypes.c_int
         L.gsr_backward_blend.argtypes = [ctypes.POINTER(Camera), ctypes.POINTER(Gaussians),
                                          ctypes.POINTER(Settings), ctypes.POINTER(Buffers), vp, ALLOC_FN, vp,
@@ -169,10 +188,10 @@ def load_hip() -> ctypes.CDLL:
                                          i32, pi32, i32, vp, vp, ctypes.POINTER(Grads), vp]
         L.gsr_view.restype = vp
         L.gsr_view.argtypes = [ctypes.POINTER(Camera), i32, ctypes.POINTER(Buffers), ctypes.c_int]
-        for n in ("gsr_geom_bytes", "gsr_scratch_bytes"):
+        for n in ("gsr_geom_bytes", "gsr_scratch_bytes", "gsr_scratch_bytes_aux"):
             getattr(L, n).restype = ctypes.c_size_t
             getattr(L, n).argtypes = [i32]
-        for n in ("gsr_binning_bytes", "gsr_ck_pool_slots"):
+        for n in ("gsr_binning_bytes", "gsr_ck_pool_slots", "gsr_binning_bytes_aux"):
             getattr(L, n).restype = ctypes.c_size_t
             getattr(L, n).argtypes = [i32, i32, i32]
         L.gsr_profile_enable.restype = ctypes.c_int
@@ -183,6 +202,8 @@ def load_hip() -> ctypes.CDLL:
         L.gsr_stage_name.argtypes = [ctypes.c_int]
         L.gsr_image_bytes.restype = ctypes.c_size_t
         L.gsr_image_bytes.argtypes = [i32, i32]
+        L.gsr_image_bytes_aux.restype = ctypes.c_size_t
+        L.gsr_image_bytes_aux.argtypes = [i32, i32]
         # gsr_train.h
         f32 = ctypes.c_float
         L.gsr_activate.restype = ctypes.c_int

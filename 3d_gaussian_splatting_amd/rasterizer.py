@@ -74,6 +74,8 @@ class ForwardState:
     color: torch.Tensor
     radii: torch.Tensor
     allocs: list = field(default_factory=list)
+    depth: torch.Tensor | None = None   # forward_aux: (H, W) sum w v (v = z, or 1 / z)
+    alpha: torch.Tensor | None = None   # forward_aux: (H, W) sum w = 1 - final T
 
     @property
     def num_rendered(self) -> int:
@@ -265,6 +267,49 @@ class CAbiRasterizer:
         self._check(rc, "gsr_forward")
         return ForwardState(cam=cam, inputs=inputs, settings=s, gauss=g, buffers=bufs, color=color,
                             radii=radii, allocs=[ag, ab, ai])
+
+    def forward_aux(self, cam: RasterCamera, means3D, opacities, scales=None, rotations=None, sh_dc=None,
+                    sh_rest=None, sh_degree=0, colors_precomp=None, cov3D_precomp=None, scale_modifier=1.0,
+                    bg=(0.0, 0.0, 0.0), tile_rows=None, max_rendered=0, debug=False,
+                    inverse_depth=False) -> ForwardState:
+        """gsr_forward_aux: forward() plus .depth = sum w z (sum w / z with inverse_depth) and
+        .alpha = sum w per pixel, over the pairs the colour pass blends.  Full images only."""
+        dev = self.device
+        inputs, g, s = self._prepare(means3D, opacities, scales, rotations, sh_dc, sh_rest, sh_degree,
+                                     colors_precomp, cov3D_precomp, scale_modifier, bg, tile_rows, max_rendered,
+                                     debug)
+        s.flags |= native.GSR_FLAG_AUX | (native.GSR_FLAG_INVDEPTH if inverse_depth else 0)
+        P = g.P
+        color = torch.empty((3, cam.height, cam.width), dtype=torch.float32, device=dev)
+        depth = torch.empty((cam.height, cam.width), dtype=torch.float32, device=dev)
+        alpha = torch.empty((cam.height, cam.width), dtype=torch.float32, device=dev)
+        radii = torch.empty((P,), dtype=torch.int32, device=dev)
+        ag, ab, ai = _Allocator(dev), _Allocator(dev), _Allocator(dev)
+        bufs = native.Buffers()
+        aux = native.AuxOut(depth.data_ptr(), alpha.data_ptr())
+        c = self._cam(cam)
+        rc = self.L.gsr_forward_aux(ctypes.byref(c), ctypes.byref(g), ctypes.byref(s), _ptr(color),
+                                    _ptr(radii) if P else None, ag.cb, ab.cb, ai.cb, None, ctypes.byref(bufs),
+                                    self._stream(), ctypes.byref(aux))
+        self._check(rc, "gsr_forward_aux")
+        return ForwardState(cam=cam, inputs=inputs, settings=s, gauss=g, buffers=bufs, color=color,
+                            radii=radii, allocs=[ag, ab, ai], depth=depth, alpha=alpha)
+
+    def backward_aux(self, st: ForwardState, dL_dpix, dL_ddepth=None, dL_dalpha=None) -> dict:
+        """gsr_backward_aux: backward() for a loss over colour, depth and alpha (None = zero)."""
+        H, W = st.cam.height, st.cam.width
+        dpix = _f32(dL_dpix, (3, H, W), self.device)
+        dd = _f32(dL_ddepth, (H, W), self.device)
+        da = _f32(dL_dalpha, (H, W), self.device)
+        out, gg = self._grad_tensors(st)
+        scratch = _Allocator(self.device)
+        aux = native.AuxGrads(None if dd is None else dd.data_ptr(), None if da is None else da.data_ptr())
+        c = self._cam(st.cam)
+        rc = self.L.gsr_backward_aux(ctypes.byref(c), ctypes.byref(st.gauss), ctypes.byref(st.settings),
+                                     ctypes.byref(st.buffers), _ptr(dpix), scratch.cb, None, ctypes.byref(gg),
+                                     self._stream(), ctypes.byref(aux))
+        self._check(rc, "gsr_backward_aux")
+        return out
 
     def forward_batch(self, cams, means3D, opacities, scales=None, rotations=None, sh_dc=None, sh_rest=None,
                       sh_degree=0, colors_precomp=None, cov3D_precomp=None, scale_modifier=1.0,
@@ -552,6 +597,21 @@ def ext_camera(cam: RasterCamera):
                             [float(v) for v in cam.campos])
 
 
+def rasterize_gaussians_aux(cam: RasterCamera, means3D, means2D, opacities, sh_dc=None, sh_rest=None,
+                            colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None,
+                            sh_degree=0, scale_modifier=1.0, bg=(0.0, 0.0, 0.0), tile_rows=None, debug=False,
+                            max_rendered=0, inverse_depth=False):
+    """RasterizeGaussiansAux.apply: returns (color (3,H,W), depth (H,W), alpha (H,W), radii (P,)
+    int32).  color, depth and alpha are differentiable in every tensor input; depth = sum w z
+    (sum w / z with inverse_depth), alpha = sum w, un-normalised (expected depth = depth / alpha)."""
+    ext = native.load_torch_ext()
+    y0, y1 = (0, INT32_MAX) if tile_rows is None else tile_rows
+    rs = ext.RasterSettings([float(v) for v in bg], float(scale_modifier), int(sh_degree), int(y0), int(y1),
+                            bool(debug), int(max_rendered))
+    return ext.rasterize_gaussians_aux(ext_camera(cam), rs, bool(inverse_depth), means3D, means2D, sh_dc, sh_rest,
+                                       colors_precomp, opacities, scales, rotations, cov3D_precomp)
+
+
 def rasterize_gaussians(cam: RasterCamera, means3D, means2D, opacities, sh_dc=None, sh_rest=None,
                         colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None,
                         sh_degree=0, scale_modifier=1.0, bg=(0.0, 0.0, 0.0), tile_rows=None, debug=False,
@@ -575,9 +635,11 @@ class PipelineParams:
 
 
 def render(viewpoint_camera: RasterCamera, pc, pipe: PipelineParams, bg_color, scaling_modifier=1.0,
-           override_color=None) -> dict:
+           override_color=None, return_depth=False, inverse_depth=False) -> dict:
     """render(): same contract as the C++ gsr::render template (csrc/torch/gsr_render.h) for a
-    model exposing the reference GaussianModel getters (see model.GaussianModel)."""
+    model exposing the reference GaussianModel getters (see model.GaussianModel).  return_depth
+    adds the differentiable keys "depth" (sum w z, or sum w / z with inverse_depth) and "alpha"
+    (sum w); without it the dict and the kernels launched are the colour-only ones."""
     from .general import eval_sh
     xyz = pc.get_xyz
     screenspace = torch.zeros_like(xyz, requires_grad=True)
@@ -596,9 +658,13 @@ def render(viewpoint_camera: RasterCamera, pc, pipe: PipelineParams, bg_color, s
         colors = torch.clamp_min(eval_sh(pc.active_sh_degree, pc.get_features, dirs) + 0.5, 0.0)
     else:
         sh_dc, sh_rest = pc.features_dc, pc.features_rest
-    color, radii = rasterize_gaussians(viewpoint_camera, xyz, screenspace, pc.get_opacity, sh_dc=sh_dc,
-                                       sh_rest=sh_rest, colors_precomp=colors, scales=scales,
-                                       rotations=rotations, cov3D_precomp=cov3D,
-                                       sh_degree=0 if colors is not None else pc.active_sh_degree,
-                                       scale_modifier=scaling_modifier, bg=bg, debug=pipe.debug)
+    kw = dict(sh_dc=sh_dc, sh_rest=sh_rest, colors_precomp=colors, scales=scales, rotations=rotations,
+              cov3D_precomp=cov3D, sh_degree=0 if colors is not None else pc.active_sh_degree,
+              scale_modifier=scaling_modifier, bg=bg, debug=pipe.debug)
+    if return_depth:
+        color, depth, alpha, radii = rasterize_gaussians_aux(viewpoint_camera, xyz, screenspace, pc.get_opacity,
+                                                             inverse_depth=inverse_depth, **kw)
+        return dict(render=color, viewspace_points=screenspace, visibility_filter=radii > 0, radii=radii,
+                    depth=depth, alpha=alpha)
+    color, radii = rasterize_gaussians(viewpoint_camera, xyz, screenspace, pc.get_opacity, **kw)
     return dict(render=color, viewspace_points=screenspace, visibility_filter=radii > 0, radii=radii)

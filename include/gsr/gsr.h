@@ -51,7 +51,7 @@ extern "C" {
 
 #define GSR_ABI_VERSION 4
 #define GSR_TILE 16 /* screen tiles are GSR_TILE x GSR_TILE pixels */
-#define GSR_GRAD2D_STRIDE 12 /* floats per Gaussian in a grad2d buffer (9 used) */
+#define GSR_GRAD2D_STRIDE 12 /* floats per Gaussian in a grad2d buffer (9 used; 10 by gsr_backward_aux) */
 
 /* flags */
 #define GSR_FLAG_DEBUG 1u /* synchronise + check after every stage */
@@ -60,6 +60,11 @@ extern "C" {
  * the splats any band cut [r0, r1) receives are sum_{y<r1} starts - sum_{y<r0} ends, so a
  * multi-GPU step re-plans its cuts and capacities from a step's own statistics (no probe). */
 #define GSR_FLAG_ROW_SPANS 2u
+/* gsr_forward_aux / gsr_backward_aux only (set by those calls themselves; no other call reads
+ * them): the forward also blends a depth and an alpha channel; the depth channel carries 1 / z
+ * instead of z. */
+#define GSR_FLAG_AUX 4u
+#define GSR_FLAG_INVDEPTH 8u
 #define GSR_ERR_OVERFLOW (-4) /* gsr_read_num_rendered: K exceeded the binning's capacity */
 
 typedef struct gsr_camera {
@@ -130,6 +135,9 @@ typedef struct gsr_buffers {
 #define GSR_LAYOUT_TAG_MASK 0xFFFF0000u
 #define GSR_LAYOUT_ROW_BUCKETED 1u      /* row-bucketed binning (tile keys not stored in the step) */
 #define GSR_LAYOUT_PRESORT 2u           /* global depth pre-sort (rank-order payload) */
+#define GSR_LAYOUT_AUX 4u                /* written by gsr_forward_aux: the image / binning buffers are the
+                                           larger aux ones (depth sum plane, depth checkpoints) */
+#define GSR_LAYOUT_INVDEPTH 8u          /* with GSR_LAYOUT_AUX: that forward ran with GSR_FLAG_INVDEPTH */
 #define GSR_ERR_LAYOUT (-13)            /* gsr_buffers.layout missing or inconsistent */
 
 int gsr_abi_version(void);
@@ -195,7 +203,8 @@ int gsr_backward(const gsr_camera* cam, const gsr_gaussians* gs, const gsr_raste
                  void* alloc_ctx, const gsr_grads* grads, void* stream);
 
 /* B1 only: per-Gaussian 2D gradients into grad2d (P x GSR_GRAD2D_STRIDE floats:
- * mean2D.x, mean2D.y, conic A, B, C, opacity, r, g, b, 0, 0, 0).  Summable across tile bands
+ * mean2D.x, mean2D.y, conic A, B, C, opacity, r, g, b, 0, 0, 0; gsr_backward_aux keeps
+ * dL/dv (the depth channel's "colour" gradient) in slot 9).  Summable across tile bands
  * before gsr_backward_preprocess (zeros for Gaussians outside the band). */
 int gsr_backward_blend(const gsr_camera* cam, const gsr_gaussians* gs,
                        const gsr_raster_settings* rs, const gsr_buffers* bufs,
@@ -206,6 +215,49 @@ int gsr_backward_blend(const gsr_camera* cam, const gsr_gaussians* gs,
 int gsr_backward_preprocess(const gsr_camera* cam, const gsr_gaussians* gs,
                             const gsr_raster_settings* rs, const gsr_buffers* bufs,
                             const float* grad2d, const gsr_grads* grads, void* stream);
+
+/* ---- Depth and alpha outputs ----
+ * gsr_forward_aux is gsr_forward plus two more blended channels over the same (pixel, Gaussian)
+ * pairs the colour pass blends (same alpha >= 1/255 and power > 0 rejections, same T < 1e-4
+ * termination), with w_i = T_i alpha_i:
+ *   aux->depth[H x W] = sum_i w_i v_i   v_i = z_i, the f32 view-space depth F1 computes (the bits
+ *                                       of GSR_VIEW_DEPTH_KEY), or 1 / z_i when rs->flags has
+ *                                       GSR_FLAG_INVDEPTH.  Un-normalised, no background term.
+ *   aux->alpha[H x W] = sum_i w_i       (= 1 - final T).  Expected depth is depth / alpha.
+ * out_color, radii, num_rendered and the sorted list are bit-identical to gsr_forward's.  Full
+ * images only: a tile band in rs is refused (< 0, gsr_last_error).  The allocation callbacks are
+ * asked for gsr_geom_bytes, gsr_binning_bytes_aux and gsr_image_bytes_aux; bufs->layout gets
+ * GSR_LAYOUT_AUX (and GSR_LAYOUT_INVDEPTH).
+ *
+ * gsr_backward_aux is gsr_backward for a loss over all three outputs: dL_ddepth and dL_dalpha
+ * (each H x W, each nullable: NULL = zero) besides dL_dout_color.  Through alpha_i they reach
+ * dL_dmeans2D, dL_dconic, dL_dopacity and every geometry leaf; through v_i they reach dL_dmeans3D
+ * (+= dL/dz_i * (V[2], V[6], V[10]), dL/dz_i = -dL/dv_i / z_i^2 under GSR_FLAG_INVDEPTH).  It
+ * needs gsr_forward_aux's buffers (GSR_ERR_LAYOUT otherwise) and the forward's GSR_FLAG_INVDEPTH
+ * choice in rs->flags (a mismatch with the layout word is GSR_ERR_LAYOUT).  alloc_scratch is asked
+ * for two blocks: 48 * P bytes and gsr_scratch_bytes_aux(capacity).
+ *
+ * Aux buffers hold every array of the plain ones at the same offsets (the aux arrays follow
+ * them), so gsr_backward, gsr_backward_blend, gsr_backward_preprocess, gsr_read_num_rendered and
+ * gsr_view accept them as they are (colour gradients only); gsr_backward_aux does not accept
+ * plain buffers. */
+typedef struct gsr_aux_out {
+    float* depth;            /* H x W   required */
+    float* alpha;            /* H x W   required */
+} gsr_aux_out;
+
+typedef struct gsr_aux_grads {
+    const float* dL_ddepth;  /* H x W or NULL (zero) */
+    const float* dL_dalpha;  /* H x W or NULL (zero) */
+} gsr_aux_grads;
+
+int gsr_forward_aux(const gsr_camera* cam, const gsr_gaussians* gs, const gsr_raster_settings* rs,
+                    float* out_color, int32_t* radii, gsr_alloc_fn alloc_geom, gsr_alloc_fn alloc_binning,
+                    gsr_alloc_fn alloc_image, void* alloc_ctx, gsr_buffers* bufs, void* stream,
+                    const gsr_aux_out* aux);
+int gsr_backward_aux(const gsr_camera* cam, const gsr_gaussians* gs, const gsr_raster_settings* rs,
+                     const gsr_buffers* bufs, const float* dL_dout_color, gsr_alloc_fn alloc_scratch,
+                     void* alloc_ctx, const gsr_grads* grads, void* stream, const gsr_aux_grads* aux);
 
 /* ---- Multi-GPU: Gaussian shards x tile-row bands (the scaling version) ----
  * Rank r of N owns the Gaussian shard [g0_r, g1_r) (contiguous, in rank order) and the band
@@ -339,6 +391,11 @@ size_t gsr_binning_bytes(int32_t capacity, int32_t width, int32_t height);
 size_t gsr_ck_pool_slots(int32_t capacity, int32_t width, int32_t height);
 size_t gsr_image_bytes(int32_t width, int32_t height);
 size_t gsr_scratch_bytes(int32_t capacity);
+/* ... and by gsr_forward_aux / gsr_backward_aux: the image buffer has one more H x W plane (the
+ * depth sum), every checkpoint slot 1 KB more (the depth sum so far), every partial entry 4 B more. */
+size_t gsr_binning_bytes_aux(int32_t capacity, int32_t width, int32_t height);
+size_t gsr_image_bytes_aux(int32_t width, int32_t height);
+size_t gsr_scratch_bytes_aux(int32_t capacity);
 
 #ifdef __cplusplus
 }
