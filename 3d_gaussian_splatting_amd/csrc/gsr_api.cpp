@@ -224,15 +224,13 @@ struct Views {
     uint32_t *free_k, *free_v;           // the other ping-pong pair (scratch after the sort)
 };
 
-// The layout word a forward of n entries over gx x gy tiles, `ntiles` of them binned, with a
-// binning of `cap` instances writes (fwd_phase2): the row-bucketed binning where the image fits
-// it and the per-tile depth order can take it, the pre-sort on dense images.
-uint32_t expected_layout(long long n, int gx, int gy, long long cap, int ntiles) {
+// The layout word a forward of n entries over gx x gy tiles with a binning of `cap` instances
+// writes (fwd_phase2): the row-bucketed binning where the image fits it, the pre-sort on dense
+// images.
+uint32_t expected_layout(long long n, int gx, int gy, long long cap) {
     uint32_t w = GSR_LAYOUT_TAG;
     if (use_presort(n, gx, gy)) w |= kBufPresort;
-    if (use_rb_binning(n, gx, gy) && cap > 0 && cap < kRbMaxCap &&
-        (GSR_RB_DEEP || tile_wave_sort_eligible(cap, ntiles)))
-        w |= kBufRowBucketed;
+    if (use_rb_binning(n, gx, gy) && cap > 0 && cap < kRbMaxCap) w |= kBufRowBucketed;
     return w;
 }
 
@@ -246,7 +244,7 @@ int check_layout(const gsr_camera* cam, int ty0, int ty1, const gsr_buffers* b) 
                     "unchanged",
                     b->layout, GSR_ABI_VERSION);
     const int gx = div_up(cam->width, kTile), gy = div_up(cam->height, kTile);
-    const uint32_t want = expected_layout(b->n_local, gx, gy, b->capacity, (ty1 - ty0) * gx);
+    const uint32_t want = expected_layout(b->n_local, gx, gy, b->capacity);
     // the aux bits say which forward sized the buffers; aux buffers hold the plain arrays at the
     // plain offsets, so every plain use accepts them (gsr_backward_aux asks for the bits itself)
     if ((b->layout & ~(kBufAux | kBufInvDepth)) != want || (b->layout & (kBufAux | kBufInvDepth)) == kBufInvDepth)
@@ -406,11 +404,11 @@ int fwd_phase2(FwdJob& j, long long cap, gsr_alloc_fn alloc_binning, void* ctx, 
                                                  j.aux != nullptr).total);
     if (!bufs->binning) return fail(-2, "allocation failed (binning, %lld instances)", cap);
     const int tiles = j.gx * j.gy, ntiles = (j.ty1 - j.ty0) * j.gx;
-    // Row-bucketed binning when the image fits it and the register form takes the per-tile depth
-    // order (it leaves a tile's entries unordered, which that form does not mind); recorded in the
-    // buffers so that every later view of them (backward, accessors) finds the same arrays.
+    // Row-bucketed binning when the image fits it (it leaves a tile's entries unordered: the
+    // per-tile depth order sorts them by the whole (depth, gid) key); recorded in the buffers so
+    // that every later view of them (backward, accessors) finds the same arrays.
     const bool scanned = use_rb_binning(j.n, j.gx, j.gy);  // phase 1 ran the three-kernel scan
-    bufs->layout = expected_layout(j.n, j.gx, j.gy, cap, ntiles) | j.aux_bits();
+    bufs->layout = expected_layout(j.n, j.gx, j.gy, cap) | j.aux_bits();
     const Views v = views(cam, j.n, bufs);
     if (v.presort)
         GSR_STAGE(GSR_STAGE_DUPLICATE, launch_duplicate_ranked(v.rtiles, v.rrect, v.rect, (int)j.n, j.gx, j.ty0,
@@ -432,13 +430,12 @@ int fwd_phase2(FwdJob& j, long long cap, gsr_alloc_fn alloc_binning, void* ctx, 
         // columns in the checkpoint pool (which F6 fills only after the sort; used when it holds cap
         // words), pass B's instances as (gid, key) over kB..vB, and the per-tile sort writes the
         // ordered gids to vA -- one 8-B store per pair / instance and no key gather in the sort.
-        const bool rb_keys = GSR_RB_SORT_KEYS && !GSR_RB_TILE_KEYS && v.ck_bytes >= 4 * (size_t)cap;
+        const bool rb_keys = v.ck_bytes >= 4 * (size_t)cap;
         uint2* const ppair = rb_keys ? reinterpret_cast<uint2*>(v.kA) : nullptr;
         uint2* const tpair = rb_keys ? reinterpret_cast<uint2*>(v.kB) : nullptr;
         uint32_t* const pxr = rb_keys ? reinterpret_cast<uint32_t*>(v.ck) : v.vB;
         GSR_STAGE(GSR_STAGE_TILE_SORT, launch_rb_binning(v.tiles, v.rect, v.offsets, (int)j.n, j.gx, j.ty0, j.ty1,
-                                                         v.rb_histA, v.rb_histB, v.rb_status, v.kB, pxr,
-                                                         GSR_RB_TILE_KEYS ? v.kA : nullptr, v.vA,
+                                                         v.rb_histA, v.rb_histB, v.rb_status, v.kB, pxr, v.vA,
                                                          v.ranges, cap, stream, j.rows_counted,
                                                          j.rows_counted ? v.lookback + 16 : nullptr, v.K_dev,
                                                          v.depth_key, ppair, tpair),
@@ -540,26 +537,21 @@ int blend_backward(const gsr_camera* cam, const gsr_raster_settings* rs, const g
                                                                  v.term, v.ck, v.ckz, stream, v.mk),
                   "blend backward (aux)");
         GSR_STAGE(GSR_STAGE_GATHER, launch_gather_grad2d(v.offsets, partial, v.rec, cam->width, cam->height, cap,
-                                                         (int)n, v.presort ? v.rrect : nullptr, grad2d, stream, 1,
-                                                         true),
+                                                         (int)n, v.presort ? v.rrect : nullptr, grad2d, stream, true),
                   "gather grad2d (aux)");
         return 0;
     }
-    // band launches split each (tile, chunk) of B1 over `split` waves by stripe, one partial
-    // entry per (instance, part)
-    int split = b1_split(cam->width, cam->height, ty0, ty1, vgy);
-    if (cap * split > (long long)UINT32_MAX) split = 1;  // entry indices are u32
-    float* partial = static_cast<float*>(alloc_scratch(ctx, PartLayout(cap * split).total));
+    float* partial = static_cast<float*>(alloc_scratch(ctx, PartLayout(cap).total));
     if (!partial) return fail(-2, "allocation failed (scratch, %lld instances)", cap);
     // only the per-entry flag bytes are zeroed: the gather reads the entries B1 flagged
-    GSR_STAGE(GSR_STAGE_MISC, launch_clear_flags(partial, cap * split, stream), "clear partial flags");
+    GSR_STAGE(GSR_STAGE_MISC, launch_clear_flags(partial, cap, stream), "clear partial flags");
     GSR_STAGE(GSR_STAGE_BLEND_BWD, launch_blend_backward(*cam, rs->bg, ty0, ty1, v.ranges, v.sorted_gid, v.rect, v.rec,
                                                          v.final_T, v.accum, dL_dpix, partial, cap, v.term, v.ck,
-                                                         stream, vgy, vh, v.mk, split),
+                                                         stream, vgy, vh, v.mk),
               "blend backward");
     GSR_STAGE(GSR_STAGE_GATHER, launch_gather_grad2d(v.offsets, partial, v.rec, cam->width, vgy > 0 ? vh : cam->height,
                                                      cap, (int)n,
-                                                     v.presort ? v.rrect : nullptr, grad2d, stream, split),
+                                                     v.presort ? v.rrect : nullptr, grad2d, stream),
               "gather grad2d");
     return 0;
 }
@@ -1185,7 +1177,7 @@ const void* gsr_view(const gsr_camera* cam, int32_t P, const gsr_buffers* bufs, 
     switch (what) {
         case GSR_VIEW_SORTED_GID: return v.sorted_gid;
         case GSR_VIEW_SORTED_TILE:
-            if (v.rb && !GSR_RB_TILE_KEYS && bufs->binning && bufs->capacity > 0) {
+            if (v.rb && bufs->binning && bufs->capacity > 0) {
                 // filled here from the ranges between two device-wide waits: the forward may have
                 // run on any stream, blocking or not (a torch pool stream, torch.cuda.stream(s)), and
                 // the null stream alone is not ordered after a non-blocking one; both

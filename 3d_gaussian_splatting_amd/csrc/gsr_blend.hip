@@ -161,26 +161,12 @@ __device__ __forceinline__ float pair_alpha_keep(float e, float L, float& oG, bo
 // T - alpha T (the reference's T (1 - alpha), one op shorter) is >= 1e-4; otherwise the pixel
 // terminates with T unchanged (SURVEY B.3 / forward.cu renderCUDA).  The exponent is
 // Horner-form: ((c' dy + b' dx) dy) + (a' dx^2 + log2 o), 3 ops per stripe with dy.
-#ifndef GSR_F6_ONESYNC
-#define GSR_F6_ONESYNC 1
-#endif
-#ifndef GSR_CK_MERGE
-#define GSR_CK_MERGE 1
-#endif
-#ifndef GSR_CK_MERGE_BATCH_END
-#define GSR_CK_MERGE_BATCH_END 0
-#endif
-#ifndef GSR_F6_BATCH4
-#define GSR_F6_BATCH4 256
-#endif
-#ifndef GSR_F6_GID_AHEAD
-#define GSR_F6_GID_AHEAD 1
-#endif
+// records per batch of the four-wave (band) F6: one per thread (128: four waves sharing the
+// two-wave kernel's 128-record batches)
+constexpr int kF6Batch4 = 256;
 // two-wave (full-image) F6 held to 8 waves per SIMD (64 VGPRs): the gid-ahead register would
 // otherwise take it to 65 and 7 waves
-#ifndef GSR_F6_WPE
-#define GSR_F6_WPE 8
-#endif
+constexpr int kF6Wpe = 8;
 // Depth / alpha channel (gsr_forward_aux, gsr_backward_aux).  The aux variants of F6 and B1 are the
 // same kernels instantiated with one more trailing argument (the pack AX = {F6Aux} / {B1Aux}); with
 // the pack empty every `if constexpr (AUX)` block drops out and the kernel -- arguments, registers,
@@ -212,13 +198,11 @@ __device__ __forceinline__ float aux_value(uint32_t key, int inv) {
     const float z = __uint_as_float(key);
     return inv ? 1.0f / z : z;
 }
-// The aux F6 variants hold one more accumulator per pixel: GSR_F6_AUX_WPE waves per SIMD for the
+// The aux F6 variants hold one more accumulator per pixel: kF6AuxWpe waves per SIMD for the
 // two-wave form (DESIGN.md "Depth and alpha outputs" has the compiler's resource report)
-#ifndef GSR_F6_AUX_WPE
-#define GSR_F6_AUX_WPE 7
-#endif
+constexpr int kF6AuxWpe = 7;
 template <int NW, class... AX>
-__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 2 ? (sizeof...(AX) ? GSR_F6_AUX_WPE : GSR_F6_WPE) : 1))) void blend_forward_kernel(const BlendGeom geo,
+__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 2 ? (sizeof...(AX) ? kF6AuxWpe : kF6Wpe) : 1))) void blend_forward_kernel(const BlendGeom geo,
                                                                 const uint2* __restrict__ ranges,
                                                                 const uint32_t* __restrict__ sorted_gid,
                                                                 const float4* __restrict__ rec,
@@ -232,9 +216,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 2
     static_assert(sizeof...(AX) <= 1, "one aux argument");
     const F6Aux ax = aux_arg<F6Aux>(axp...);
     constexpr int PPL = kPPL / NW;
-    // records per batch: one per thread, or (GSR_F6_BATCH4 = 128) four waves sharing the two-wave
-    // kernel's 128-record batches -- the same live-stripe refresh points, so the same chunks
-    constexpr int BATCH = NW > 2 ? GSR_F6_BATCH4 : 64 * NW;
+    // records per batch: one per thread
+    constexpr int BATCH = NW > 2 ? kF6Batch4 : 64 * NW;
     static_assert(BATCH % 64 == 0 && BATCH <= 64 * NW, "F6 batch");
     constexpr int kCW = NW > 2 ? kBandChunkWork : kChunkWork;
     __shared__ float4 srec[BATCH * 3];
@@ -294,7 +277,6 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 2
             if (lane == 0) ckm[4 * (size_t)slot + w * PPL + p] = on ? 1 : 0;
         }
     };
-#if GSR_CK_MERGE
     // Chunk merging.  When all kMaxChunks - 1 chunk starts are taken and the current chunk is
     // full, neighbouring chunks are merged pairwise (the even starts are kept: chunk k of the
     // merged table is chunk 2k of the old one, its checkpoint moved to slot k) and the quota
@@ -328,26 +310,17 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 2
         work += quota;  // the merged current chunk: old chunk 2 kKeep (>= one quota) + the open one
         quota *= 2;
     };
-#else
-    constexpr int quota = kCW;
-#endif
-    // GSR_F6_GID_AHEAD: each batch's gid is loaded one batch ahead (one VGPR), so a batch start
-    // waits for its record loads only, not for the gid load they depend on as well
-    uint32_t g_next = GSR_F6_GID_AHEAD && tid < BATCH && tid < n ? sorted_gid[range.x + tid] : 0u;
+    // each batch's gid is loaded one batch ahead (one VGPR), so a batch start waits for its record
+    // loads only, not for the gid load they depend on as well
+    uint32_t g_next = tid < BATCH && tid < n ? sorted_gid[range.x + tid] : 0u;
     for (int base = 0; base < n; base += BATCH) {
         uint32_t live = 0;
 #pragma unroll
         for (int p = 0; p < PPL; ++p) live |= __any(T[p] > 0.0f) ? (1u << p) : 0u;
         if (lane == 0) slive[w] = live << (w * PPL);
-#if !GSR_F6_ONESYNC
-        if (__syncthreads_or(live != 0) == 0) {
-            tend = base;
-            break;
-        }
-#endif
         if (tid < BATCH && base + tid < n) {
-            const uint32_t g = GSR_F6_GID_AHEAD ? g_next : sorted_gid[range.x + base + tid];
-            if (GSR_F6_GID_AHEAD && base + BATCH + tid < n) g_next = sorted_gid[range.x + base + BATCH + tid];
+            const uint32_t g = g_next;
+            if (base + BATCH + tid < n) g_next = sorted_gid[range.x + base + BATCH + tid];
             const float4* r = rec + 3 * (size_t)g;
             const float4 r0 = r[0], r1 = r[1], r2 = r[2];
             srec[3 * tid + 0] = r0;
@@ -363,7 +336,6 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 2
         uint32_t tile_live = 0;
 #pragma unroll
         for (int i = 0; i < NW; ++i) tile_live |= slive[i];
-#if GSR_F6_ONESYNC
         // termination from the batch barrier's own slive words (__syncthreads_or is three
         // barriers); the batch just loaded is then discarded, and its mask bytes lie at or past
         // tend, where B1 never reads
@@ -371,15 +343,12 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 2
             tend = base;
             break;
         }
-#endif
         const int cnt = (n - base) < BATCH ? (n - base) : BATCH;
         int visited = 0;
         for (int c0 = 0; c0 < cnt; c0 += 64) {
             const uint32_t sm = smk[c0 + lane];  // 0 past cnt
-#if GSR_CK_MERGE && !GSR_CK_MERGE_BATCH_END
             // at the group boundary where a 32nd chunk would open
             if (__builtin_expect(work >= quota && nck == kMaxChunks - 1, 0)) merge_chunks();
-#endif
             if (work >= quota && nck < kMaxChunks - 1) {  // chunk nck + 1 starts at base + c0
                 ++nck;
                 checkpoint(ck_slot_of(geo.ck_fixed, range.x, tl, nck), live);
@@ -392,14 +361,11 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 2
             if (!live) continue;
             const uint32_t mine = (sm >> (w * PPL)) & ((1u << PPL) - 1u);
             uint64_t todo = __ballot((mine & live) != 0u && c0 + lane < cnt);
-#ifndef GSR_F6_BAND_PAIRS
-#define GSR_F6_BAND_PAIRS 1
-#endif
             // Band launches (NW = 4: one stripe per wave, every block resident at once) are bound
             // by one wave's dependent chain per record, not by issue: there two records are taken
             // per pass -- both alphas first (they do not depend on T), then the T / colour
             // updates in list order, so the result is bit-identical.
-            if constexpr (GSR_F6_BAND_PAIRS && PPL == 1) {
+            if constexpr (PPL == 1) {
                 while (todo) {
                     const int ka = c0 + __builtin_ctzll(todo);
                     todo &= todo - 1;
@@ -489,10 +455,6 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 2
                 }
             }
         }
-#if GSR_CK_MERGE && GSR_CK_MERGE_BATCH_END
-        // at the end of the batch in which the last start was taken (outside the blend loop)
-        if (nck == kMaxChunks - 1) merge_chunks();
-#endif
         __syncthreads();
     }
     if (tid == 0) {
@@ -594,36 +556,20 @@ __device__ __forceinline__ void park_flush(const float* qpark, const uint32_t* s
 // chunk-major, so every tile's first chunk is dispatched first.
 // 6 waves per SIMD: 80 VGPRs (no spills) and 6.2 KB of LDS per one-wave block.  Measured
 // 0.552 ms vs 0.564 at the compiler's own 85 VGPRs (5 waves); 7 and 8 waves spill.
-// Mask bytes per lane in one batch window (4: 256 entries per window; 16: 1024, for lists whose
-// entries are mostly culled, e.g. after an opacity reset -- fewer serial window loads).
-#ifndef GSR_B1_PAIRS
-#define GSR_B1_PAIRS 0
-#endif
-// GSR_B1_GID_WIN: B1 loads the batch window's gids with its mask bytes (one 16-B load per lane),
-// so a batch's record loads do not wait on a gid load first
-#ifndef GSR_B1_GID_WIN
-#define GSR_B1_GID_WIN 1
-#endif
-constexpr int kB1Win = GSR_B1_WIN;
-static_assert(kB1Win == 4 || kB1Win == 16, "B1 window: 4 or 16 mask bytes per lane");
-// SPW: the 16x4 stripes one wave owns.  4 (full images): one wave per (tile, chunk) and one
-// partial entry per (tile, instance).  2 or 1 (band launches, b1_split): the (tile, chunk) is
-// split over 4 / SPW one-wave blocks by stripe ("parts"), each running the same front-to-back
-// loop over its own pixels only -- its own termination, its own visit filter -- and writing
-// its own partial entry j * parts + part, which the gather sums with the others in part order.
-// A band of 1/8 of the tiles then still fills the chip (~3.3 chunks per tile leave ~3 one-wave
-// blocks per SIMD otherwise), at the price of per-record work repeated per part.
-// PF (band launches, GSR_B1_BAND_PREFETCH): each visited record's LDS reads are issued before the
+// kB1Win (gsr_internal.h) mask bytes per lane in one batch window: 256 entries per window.  B1
+// loads the window's gids with its mask bytes (one 16-B load per lane), so a batch's record
+// loads do not wait on a gid load first.
+// One wave per (tile, chunk) owns the tile's four 16x4 stripes and writes one partial entry per
+// (tile, instance).
+// PF (band launches): each visited record's LDS reads are issued before the
 // previous record's work (2x unrolled, no register copies) -- with ~3 one-wave blocks per SIMD on a
 // band's 1020 tiles the LDS latency per record is exposed, where on full images other waves hide
 // it (round 4: the same prefetch at full occupancy measured 0.456 vs 0.447 ms).
-// The aux B1 variants (SPW = 4 only) keep dL/ddepth per pixel and a tenth moment: GSR_B1_AUX_WPE
+// The aux B1 variants keep dL/ddepth per pixel and a tenth moment: kB1AuxWpe
 // waves per SIMD (DESIGN.md "Depth and alpha outputs")
-#ifndef GSR_B1_AUX_WPE
-#define GSR_B1_AUX_WPE 5
-#endif
-template <int SPW, bool PF = false, class... AX>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PF ? 4 : (SPW == 4 ? (sizeof...(AX) ? GSR_B1_AUX_WPE : 6) : 8)))) void blend_backward_kernel(const BlendGeom geo,
+constexpr int kB1AuxWpe = 5;
+template <bool PF = false, class... AX>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PF ? 4 : (sizeof...(AX) ? kB1AuxWpe : 6)))) void blend_backward_kernel(const BlendGeom geo,
                                                             const uint2* __restrict__ ranges,
                                                             const uint32_t* __restrict__ sorted_gid,
                                                             const uint4* __restrict__ rect,
@@ -638,7 +584,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PF ? 4 : (SP
                                                             const float4* __restrict__ ck,
                                                             const uint8_t* __restrict__ mk, const AX... axp) {
     constexpr bool AUX = sizeof...(AX) > 0;
-    static_assert(sizeof...(AX) <= 1 && (!AUX || SPW == 4), "one aux argument, full-image B1 only");
+    static_assert(sizeof...(AX) <= 1, "one aux argument");
+    constexpr int SPW = kPPL;  // the wave's stripes: all of the tile's
     const B1Aux ax = aux_arg<B1Aux>(axp...);
     __shared__ float svz[AUX ? 64 : 1];  // aux: the batch's v_i (unused, so absent, otherwise)
     // One block of LDS with srec first: the record fields then sit within the immediate offsets
@@ -649,22 +596,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PF ? 4 : (SP
         float qpark[kPark * kParkSlot];    // [slot][quad][9 of 12]
         uint32_t sidx[64];                 // the batch's entries (list offsets), in list order
         uint32_t smv[64];                  // and their stripe masks
-#if GSR_B1_GID_WIN
         uint32_t sgd[64];                  // and their gids (loaded with the window's mask bytes)
-#endif
     } lds;
     float4* const srec = lds.srec;
     uint32_t* const sjl = lds.sjl;
     float* const qpark = lds.qpark;
-    constexpr int S = kPPL / SPW;  // parts per (tile, chunk)
-    static_assert(SPW == 4 || SPW == 2 || SPW == 1, "stripes per wave");
     const int lane = threadIdx.x;
     float* const qlane = qpark + (lane >> 2) * 12;  // this quad's parking row
     int tl, chunk;
-    const int part = (int)((blockIdx.x / 8) % S);  // the (tile, chunk)'s parts are neighbours
-    const int sp0 = part * SPW;                      // this wave's first stripe
     {
-        const int q = geo.nwg / 8, r = geo.nwg % 8, xcd = blockIdx.x % 8, local = (int)((blockIdx.x / 8) / S);
+        const int q = geo.nwg / 8, r = geo.nwg % 8, xcd = blockIdx.x % 8, local = (int)(blockIdx.x / 8);
         const int t0 = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q, nt = q + (xcd < r ? 1 : 0);
         const int per = q + 1;  // padded tiles per XCD
         chunk = local / per;
@@ -694,7 +635,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PF ? 4 : (SP
     const int px = tx * kTile + col;
     const float pfx = (float)px;
     const int view = ty / geo.vgy, tyl = ty - view * geo.vgy;  // tile row inside its view's band
-    const float bx0 = (float)(tx * kTile), by0 = (float)(tyl * kTile);
     // F6's per-view planes (one image: view 0)
     const size_t npix = (size_t)geo.W * geo.vh;
     final_T += (size_t)view * npix;
@@ -711,7 +651,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PF ? 4 : (SP
     float dpz[SPW], v0[SPW], azS[SPW], azT[SPW], azA[SPW];
 #pragma unroll
     for (int p = 0; p < SPW; ++p) {
-        const int pyl = tyl * kTile + row + 4 * (sp0 + p);
+        const int pyl = tyl * kTile + row + 4 * p;
         pfy[p] = (float)pyl;
         const bool in = px < geo.W && pyl < geo.vh;
         const size_t pix = in ? (size_t)pyl * geo.W + px : 0;
@@ -746,11 +686,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PF ? 4 : (SP
             reinterpret_cast<const uint8_t*>(ck + (size_t)geo.ck_slots * 256) + 4 * slot);
 #pragma unroll
         for (int p = 0; p < SPW; ++p) {
-            if ((on >> (8 * (sp0 + p))) & 0xFFu) {  // wave-uniform
-                const float4 c4 = src[64 * (sp0 + p) + col + 16 * row];  // F6's lane of this pixel
+            if ((on >> (8 * p)) & 0xFFu) {  // wave-uniform
+                const float4 c4 = src[64 * p + col + 16 * row];  // F6's lane of this pixel
                 T[p] = c4.x;
                 R[p] -= fmaf(c4.y, dp0[p], fmaf(c4.z, dp1[p], c4.w * dp2[p]));
-                if constexpr (AUX) azS[p] -= ax.ckz[slot * 256 + 64 * (sp0 + p) + col + 16 * row];
+                if constexpr (AUX) azS[p] -= ax.ckz[slot * 256 + 64 * p + col + 16 * row];
             } else {
                 T[p] = -1.0f;
             }
@@ -773,33 +713,24 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PF ? 4 : (SP
     for (int base = start; base < n_lim;) {
         uint32_t live = 0;  // in stripe positions (the mask bytes' bits)
 #pragma unroll
-        for (int p = 0; p < SPW; ++p) live |= __any(T[p] > 0.0f) ? (1u << (sp0 + p)) : 0u;
+        for (int p = 0; p < SPW; ++p) live |= __any(T[p] > 0.0f) ? (1u << p) : 0u;
         if (live == 0) break;
         // the batch: up to 64 entries with a live stripe among the next 256 (four mask bytes
         // per lane from one aligned word), in list order; the next batch starts after the last
         // one taken, or after the window
-        constexpr int kW = kB1Win / 4;  // mask words per lane
+        static_assert(kB1Win == 4, "one mask word and four gids per lane");
         const uint32_t a0 = (range.x + (uint32_t)base) & ~(uint32_t)(kB1Win - 1);  // aligned window start
-        uint32_t wd[kW];
-        if constexpr (kW == 4) {
-            const uint4 v = *reinterpret_cast<const uint4*>(mk + a0 + kB1Win * lane);
-            wd[0] = v.x, wd[1] = v.y, wd[2] = v.z, wd[3] = v.w;
-        } else {
-            wd[0] = *reinterpret_cast<const uint32_t*>(mk + a0 + 4 * lane);
-        }
-#if GSR_B1_GID_WIN
-        static_assert(kB1Win == 4, "gids with the mask window: 4 entries per lane");
+        const uint32_t wd = *reinterpret_cast<const uint32_t*>(mk + a0 + 4 * lane);
         // the window's gids beside its mask bytes (one 16-B load per lane; the list array is
         // followed by the rest of the binning buffer, so the window's tail past the list is
         // readable and never used): the batch's record loads then wait for no gid load
         const uint4 gw = *reinterpret_cast<const uint4*>(sorted_gid + a0 + 4 * lane);
         const uint32_t gwa[4] = {gw.x, gw.y, gw.z, gw.w};
-#endif
         uint32_t vis = 0;
 #pragma unroll
         for (int i = 0; i < kB1Win; ++i) {
             const int e = (int)(a0 + kB1Win * lane + i - range.x);  // list offset of byte i
-            const uint32_t m = (wd[i >> 2] >> (8 * (i & 3))) & 0xFu;
+            const uint32_t m = (wd >> (8 * i)) & 0xFu;
             if (e >= base && e < n_lim && (m & live)) vis |= 1u << i;
         }
         const uint32_t c = (uint32_t)__popc(vis);
@@ -818,10 +749,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PF ? 4 : (SP
             if ((vis >> i) & 1u) {
                 if (pos < 64u) {
                     lds.sidx[pos] = a0 + kB1Win * lane + i - range.x;
-                    lds.smv[pos] = (wd[i >> 2] >> (8 * (i & 3))) & 0xFu;
-#if GSR_B1_GID_WIN
+                    lds.smv[pos] = (wd >> (8 * i)) & 0xFu;
                     lds.sgd[pos] = gwa[i];
-#endif
                 }
                 ++pos;
             }
@@ -835,18 +764,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PF ? 4 : (SP
         }
         uint32_t jl = 0, smask = 0;
         if (lane < cnt) {
-#if GSR_B1_GID_WIN
             const uint32_t g = lds.sgd[lane];
-#else
-            const uint32_t g = sorted_gid[range.x + lds.sidx[lane]];
-#endif
             const uint4 rr = rect[g];
             const int minx = rr.x & 0xFFFF, miny = rr.x >> 16, maxx = rr.y & 0xFFFF;
             const int y0 = miny > geo.ty0 ? miny : geo.ty0;
             jl = rr.z + (uint32_t)((ty - y0) * (maxx - minx) + (tx - minx));
             // past the capacity: an overflowing binning (the row-bucketed one keeps list
             // positions, not emission indices, below it) -- the entry is not written
-            jl = jl >= geo.cap ? 0xFFFFFFFFu : jl * S + part;  // this part's entry
+            if (jl >= geo.cap) jl = 0xFFFFFFFFu;
             const float4* r = rec + 3 * (size_t)g;
             srec[3 * lane + 0] = r[0];
             srec[3 * lane + 1] = r[1];
@@ -892,51 +817,19 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PF ? 4 : (SP
                 sy += svy;
                 syy = fmaf(svy, dy, syy);
             };
-#if GSR_B1_PAIRS
-            if constexpr (SPW >= 2) {
-                // Stripes in pairs (2q, 2q + 1): the two alpha / transmittance chains of a visited
-                // pair in one block, interleaved (the exp latency of one covers the other), the
-                // contributions still behind exec-mask branches.  A stripe of the pair that the
-                // record does not visit runs with L = -inf: keep is false, so alpha = 0, T stays
-                // (live T >= 1e-4, dead T < 0) and nothing is added -- bit-identical to skipping it.
 #pragma unroll
-                for (int q = 0; q < SPW / 2; ++q) {
-                    const int pa = 2 * q, pb = 2 * q + 1;
-                    const uint32_t pm = (m >> (sp0 + pa)) & 3u;
-                    if (!pm) continue;  // wave-uniform
-                    const float La = (pm & 1u) ? r2.w : -INFINITY, Lb = (pm & 2u) ? r2.w : -INFINITY;
-                    const float dya = r0.y - pfy[pa], dyb = r0.y - pfy[pb];
-                    const float ea = fmaf(fmaf(r1.x, dya, bdx), dya, K);
-                    const float eb = fmaf(fmaf(r1.x, dyb, bdx), dyb, K);
-                    float oGa, oGb;
-                    bool keepa, keepb;
-                    const float aa = pair_alpha_keep(ea, La, oGa, keepa);
-                    const float ab = pair_alpha_keep(eb, Lb, oGb, keepb);
-                    const float wa = aa * T[pa], wb = ab * T[pb];
-                    const float tTa = T[pa] - wa, tTb = T[pb] - wb;
-                    const bool oka = tTa >= 0.0001f, okb = tTb >= 0.0001f;
-                    if (oka && keepa) contribute(pa, aa, wa, oGa, dya);
-                    T[pa] = oka ? tTa : -fabsf(T[pa]);
-                    if (okb && keepb) contribute(pb, ab, wb, oGb, dyb);
-                    T[pb] = okb ? tTb : -fabsf(T[pb]);
-                }
-            } else
-#endif
-            {
-#pragma unroll
-                for (int p = 0; p < SPW; ++p) {
-                    if (!(m & (1u << (sp0 + p)))) continue;  // wave-uniform
-                    const float dy = r0.y - pfy[p];
-                    const float e = fmaf(fmaf(r1.x, dy, bdx), dy, K);
-                    float oG;
-                    bool keep;
-                    const float a = pair_alpha_keep(e, r2.w, oG, keep);
-                    const float w = a * T[p];
-                    const float tT = T[p] - w;
-                    const bool ok = tT >= 0.0001f;
-                    if (ok && keep) contribute(p, a, w, oG, dy);
-                    T[p] = ok ? tT : -fabsf(T[p]);
-                }
+            for (int p = 0; p < SPW; ++p) {
+                if (!(m & (1u << p))) continue;  // wave-uniform
+                const float dy = r0.y - pfy[p];
+                const float e = fmaf(fmaf(r1.x, dy, bdx), dy, K);
+                float oG;
+                bool keep;
+                const float a = pair_alpha_keep(e, r2.w, oG, keep);
+                const float w = a * T[p];
+                const float tT = T[p] - w;
+                const bool ok = tT >= 0.0001f;
+                if (ok && keep) contribute(p, a, w, oG, dy);
+                T[p] = ok ? tT : -fabsf(T[p]);
             }
             if (__any(any)) {
                 // the quad shares dx: reduce the six column sums (12 DPP adds, not 18 for the
@@ -963,7 +856,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PF ? 4 : (SP
             if ((++visited & 7) == 0) {
                 uint32_t lv = 0;
 #pragma unroll
-                for (int p = 0; p < SPW; ++p) lv |= __any(T[p] > 0.0f) ? (1u << (sp0 + p)) : 0u;
+                for (int p = 0; p < SPW; ++p) lv |= __any(T[p] > 0.0f) ? (1u << p) : 0u;
                 live = lv;
                 if (live == 0) return true;
             }
@@ -1017,10 +910,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PF ? 4 : (SP
 // has too few tiles to fill the chip (multi-GPU bands).  Measured at 1M/1080p with the
 // branchless stripe pair: 2 waves 0.258 ms, 1 wave 0.269 (with branches) / 0.343 (branchless,
 // 4 stripes), 4 waves 0.299.
-#ifndef GSR_F6_BAND_TILES
-#define GSR_F6_BAND_TILES 4096
-#endif
-constexpr int kF6FullWaves = 2, kF6BandWaves = 4, kF6BandTiles = GSR_F6_BAND_TILES;
+constexpr int kF6FullWaves = 2, kF6BandWaves = 4, kF6BandTiles = 4096;
 
 static BlendGeom make_geo(const gsr_camera& cam, const float bg[3], int ty0, int ty1, long long cap, int vgy, int vh) {
     BlendGeom g;
@@ -1059,55 +949,31 @@ int launch_blend_forward(const gsr_camera& cam, const float bg[3], int ty0, int 
     return (int)hipGetLastError();
 }
 
-// B1 parts per (tile, chunk) (blend_backward_kernel's 4 / SPW) on launches of fewer than
-// GSR_B1_SPLIT_TILES tiles of one image (multi-GPU bands).  Measured at 1M / 1080p, N = 8
-// (rehearsal kernel trace, mean band B1 / gather; profiles/r06_experiments/b1_split_1m_w8.txt):
-// 1 part 101.8 / 24.7 us, 2 parts 101.4 / 50.9, 4 parts 130.0 / 115.4 -- a part repeats the
-// record's set-up, batch loads and reduction for fewer stripes, and the per-chunk chain is set
-// by that per-record work, not by the stripes; so the split is built but off (1).
-#ifndef GSR_B1_SPLIT_TILES
-#define GSR_B1_SPLIT_TILES 4096
-#endif
-#ifndef GSR_B1_BAND_PREFETCH
-#define GSR_B1_BAND_PREFETCH 1
-#endif
-#ifndef GSR_B1_BAND_SPLIT
-#define GSR_B1_BAND_SPLIT 1
-#endif
-int b1_split(int W, int H, int ty0, int ty1, int vgy) {
-    (void)H;
-    const long long gx = div_up(W, kTile);
-    const long long sel = vgy > 0 ? (long long)vgy * gx : (long long)(ty1 - ty0) * gx;  // one image's tiles
-    return sel < GSR_B1_SPLIT_TILES ? GSR_B1_BAND_SPLIT : 1;
-}
-
+// B1: one one-wave block per (tile, chunk slot).  Splitting a band launch's (tile, chunk) over 2 or
+// 4 waves by stripe was measured at 1M / 1080p, N = 8 (rehearsal kernel trace, mean band B1 /
+// gather; profiles/r06_experiments/b1_split_1m_w8.txt): 1 part 101.8 / 24.7 us, 2 parts 101.4 /
+// 50.9, 4 parts 130.0 / 115.4 -- a part repeats the record's set-up, batch loads and reduction for
+// fewer stripes, and the per-chunk chain is set by that per-record work, not by the stripes.
 int launch_blend_backward(const gsr_camera& cam, const float bg[3], int ty0, int ty1,
                           const uint2* ranges, const uint32_t* sorted_gid, const uint4* rect,
                           const float4* rec, const float* final_T,
                           const float* accum, const float* dL_dpix, float* partial, long long cap,
                           const uint32_t* term, const float4* ck, hipStream_t s, int vgy, int vh,
-                          const uint8_t* mk, int split) {
+                          const uint8_t* mk) {
     const BlendGeom geo = make_geo(cam, bg, ty0, ty1, cap, vgy, vh);
     if (geo.nwg <= 0) return 0;
-    if (split != 1 && split != 2 && split != 4) return (int)hipErrorInvalidValue;
-    const PartLayout pl(cap * split);  // one entry per (instance, part)
+    const PartLayout pl(cap);
     char* base = reinterpret_cast<char*>(partial);
-    const int blocks = 8 * (geo.nwg / 8 + 1) * kMaxChunks * split;
+    const int blocks = 8 * (geo.nwg / 8 + 1) * kMaxChunks;
     auto* p8 = reinterpret_cast<float*>(base + pl.p8);
     auto* p1 = reinterpret_cast<float*>(base + pl.p1);
     auto* fl = reinterpret_cast<uint8_t*>(base + pl.fl);
     const long long sel = vgy > 0 ? (long long)geo.vgy * geo.grid_x : geo.nwg;  // one image's tiles
-    if (split == 1 && GSR_B1_BAND_PREFETCH && sel < kF6BandTiles)
-        hipLaunchKernelGGL((blend_backward_kernel<4, true>), dim3(blocks), dim3(64), 0, s, geo, ranges, sorted_gid,
+    if (sel < kF6BandTiles)
+        hipLaunchKernelGGL(blend_backward_kernel<true>, dim3(blocks), dim3(64), 0, s, geo, ranges, sorted_gid,
                            rect, rec, final_T, accum, dL_dpix, p8, p1, fl, term, ck, mk);
-    else if (split == 1)
-        hipLaunchKernelGGL(blend_backward_kernel<4>, dim3(blocks), dim3(64), 0, s, geo, ranges, sorted_gid, rect, rec,
-                           final_T, accum, dL_dpix, p8, p1, fl, term, ck, mk);
-    else if (split == 2)
-        hipLaunchKernelGGL(blend_backward_kernel<2>, dim3(blocks), dim3(64), 0, s, geo, ranges, sorted_gid, rect, rec,
-                           final_T, accum, dL_dpix, p8, p1, fl, term, ck, mk);
     else
-        hipLaunchKernelGGL(blend_backward_kernel<1>, dim3(blocks), dim3(64), 0, s, geo, ranges, sorted_gid, rect, rec,
+        hipLaunchKernelGGL(blend_backward_kernel<false>, dim3(blocks), dim3(64), 0, s, geo, ranges, sorted_gid, rect, rec,
                            final_T, accum, dL_dpix, p8, p1, fl, term, ck, mk);
     return (int)hipGetLastError();
 }
@@ -1147,11 +1013,11 @@ int launch_blend_backward_aux(const gsr_camera& cam, const float bg[3], const ui
     auto* p1 = reinterpret_cast<float*>(base + pl.p1);
     auto* fl = reinterpret_cast<uint8_t*>(base + pl.fl);
     const B1Aux ax{depth_key, accum_z, dL_ddepth, dL_dalpha, ckz, reinterpret_cast<float*>(base + pl.pz), inv ? 1 : 0};
-    if (GSR_B1_BAND_PREFETCH && geo.nwg < kF6BandTiles)
-        hipLaunchKernelGGL((blend_backward_kernel<4, true, B1Aux>), dim3(blocks), dim3(64), 0, s, geo, ranges,
+    if (geo.nwg < kF6BandTiles)
+        hipLaunchKernelGGL((blend_backward_kernel<true, B1Aux>), dim3(blocks), dim3(64), 0, s, geo, ranges,
                            sorted_gid, rect, rec, final_T, accum, dL_dpix, p8, p1, fl, term, ck, mk, ax);
     else
-        hipLaunchKernelGGL((blend_backward_kernel<4, false, B1Aux>), dim3(blocks), dim3(64), 0, s, geo, ranges,
+        hipLaunchKernelGGL((blend_backward_kernel<false, B1Aux>), dim3(blocks), dim3(64), 0, s, geo, ranges,
                            sorted_gid, rect, rec, final_T, accum, dL_dpix, p8, p1, fl, term, ck, mk, ax);
     return (int)hipGetLastError();
 }

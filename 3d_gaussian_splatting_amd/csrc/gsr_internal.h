@@ -44,10 +44,7 @@ constexpr int kRadixTile = kSortBlock * kRadixItems;
 // Sorts of fewer than kRadixSmallN keys (multi-GPU band launches, ~1M keys at 1M / 1080p, N = 8)
 // use 1024-key blocks (kRadixItemsSmall rounds per wave), so that they still launch several
 // blocks per CU.
-#ifndef GSR_RADIX_SMALL_N
-#define GSR_RADIX_SMALL_N (1 << 21)
-#endif
-constexpr long long kRadixSmallN = GSR_RADIX_SMALL_N;
+constexpr long long kRadixSmallN = 1 << 21;
 constexpr int kRadixItemsSmall = 4;
 inline int radix_tile_for(long long n) { return n < kRadixSmallN ? kSortBlock * kRadixItemsSmall : kRadixTile; }
 inline int radix_blocks(long long n) { return n > 0 ? div_up(n, radix_tile_for(n)) : 0; }
@@ -82,30 +79,13 @@ constexpr long long kPresortPerTile = GSR_PRESORT_PER_TILE;
 constexpr int kMaxViews = 8;  // gsr_forward_views: views per call (= GSR_MAX_VIEWS)
 // Row-bucketed binning (gsr_sort.hip): images of at most kRbMaxRows x kRbMaxCols tiles outside
 // presort mode; chunks of kRbChunkPairs (Gaussian, row) pairs in its second pass.
-#ifndef GSR_RB_BIN
-#define GSR_RB_BIN 1
-#endif
-// GSR_RB_TILE_KEYS 1: the row-bucketed placement writes every instance's tile key in the step
-// (0: the GSR_VIEW_SORTED_TILE accessor fills them from the ranges when asked)
-#ifndef GSR_RB_TILE_KEYS
-#define GSR_RB_TILE_KEYS 0
-#endif
-// GSR_RB_SORT_KEYS 1: the row-bucketed placement writes every instance's depth key beside its gid
-// (into the tile-key array kA, free in that mode), so the per-tile sort that follows reads its keys
-// coalesced instead of through a dependent depth_key[gid] gather per entry (round 6)
-#ifndef GSR_RB_SORT_KEYS
-#define GSR_RB_SORT_KEYS 1
-#endif
-// GSR_RB_DEEP 0: only where the per-tile sort takes its register form (mean slices <= ~1365)
-#ifndef GSR_RB_DEEP
-#define GSR_RB_DEEP 1
-#endif
+// The placement writes no tile keys (the GSR_VIEW_SORTED_TILE accessor fills them from the ranges
+// when asked); where the tile-key arrays have room it writes every instance's depth key beside its
+// gid instead (gsr_api.cpp rb_keys), so the per-tile sort that follows reads its keys coalesced
+// instead of through a dependent depth_key[gid] gather per entry (round 6).
 constexpr int kRbMaxRows = 256, kRbMaxCols = 256, kRbChunkPairs = 1024;
 // the binning's row scan splits a row into at most this many column partitions (gsr_sort.hip)
-#ifndef GSR_RB_SCAN_SPLIT
-#define GSR_RB_SCAN_SPLIT 16
-#endif
-constexpr int kRbScanSplit = GSR_RB_SCAN_SPLIT;
+constexpr int kRbScanSplit = 16;
 constexpr long long kRbMaxCap = 1LL << 30;  // the look-back's 30-bit counts (rb_tiles_scan)
 // gsr_buffers.layout (set by the forward, checked by every later use of the buffers): the tag
 // and the binning in use (gsr.h GSR_LAYOUT_*)
@@ -119,7 +99,7 @@ inline bool use_presort(long long n, int gx, int gy) {
     return presort_possible(n) && n > kPresortPerTile * (long long)gx * gy;
 }
 inline bool use_rb_binning(long long n, int gx, int gy) {
-    return GSR_RB_BIN && !use_presort(n, gx, gy) && gx <= kRbMaxCols && gy <= kRbMaxRows;
+    return !use_presort(n, gx, gy) && gx <= kRbMaxCols && gy <= kRbMaxRows;
 }
 
 struct GeomLayout {
@@ -163,9 +143,7 @@ struct GeomLayout {
 #endif
 constexpr int kMaxChunks = GSR_MAX_CHUNKS;
 // B1 batch window: mask bytes per lane (gsr_blend.hip)
-#ifndef GSR_B1_WIN
-#define GSR_B1_WIN 4
-#endif  // = GSR_TERM_STRIDE (gsr.h) in the shipped build
+constexpr int kB1Win = 4;
 
 // Checkpoint slots.  A checkpoint is 4 KB (float4 (T, C) per pixel of a tile).  A chunk opens
 // only after kChunkWork visited (record, stripe) pairs and a record has at most 4 stripes, so a
@@ -217,7 +195,7 @@ struct BinLayout {
         ckm = take(ck_slots * 4);
         // F6's stripe mask of every list entry it loads (one byte each), from which B1 picks the
         // entries it has to visit before loading any record (+ B1's 256-entry window past the end)
-        mk = take(n + 64 * GSR_B1_WIN);  // B1 reads whole windows of 64 * GSR_B1_WIN bytes
+        mk = take(n + 64 * kB1Win);  // B1 reads whole windows of 64 * kB1Win bytes
         // aux forward (depth / alpha outputs): every checkpoint's fifth value, the depth sum so far
         // (256 floats per slot, indexed like the slot's float4s), after the plain arrays
         if (aux) ckz = take(ck_slots * 256 * 4);

@@ -68,13 +68,13 @@ int launch_duplicate(const uint32_t* tiles, uint4* rect, int n, int grid_x, int 
 int launch_scan_blocks(uint32_t* bsum, int n, uint32_t* total_out, hipStream_t s);
 int launch_block_offsets(const uint32_t* tiles, int n, const uint32_t* bsum, uint32_t* offsets, hipStream_t s);
 // Row-bucketed binning (gsr_internal.h use_rb_binning): from the inclusive F2 scan `offsets`, F3
-// (inst_start into rect.z), the stable tile sort of the instances and F5 -- the (tile key, gid)
-// arrays tkey / tgid in (tile, gid) order and `ranges` (cleared beforehand) -- in two counting
+// (inst_start into rect.z), the tile sort of the instances and F5 -- the gid array tgid with
+// every tile's entries contiguous and `ranges` (cleared beforehand) -- in two counting
 // passes over (Gaussian, tile row) pairs.  histA: GeomLayout.rb_hist; histB: BinLayout.rb_hist;
 // rb_status: ImgLayout.rb_status (cleared); pgid / pxr: cap u32 each of scratch.
 int launch_rb_binning(const uint32_t* tiles, uint4* rect, uint32_t* offsets, int n, int gx, int ty0, int ty1,
                       uint32_t* histA, uint32_t* histB, uint32_t* rb_status, uint32_t* pgid, uint32_t* pxr,
-                      uint32_t* tkey, uint32_t* tgid, uint2* ranges, long long cap, hipStream_t s,
+                      uint32_t* tgid, uint2* ranges, long long cap, hipStream_t s,
                       bool rows_counted = false,     // rows_counted: F1 wrote histA (PreOut.rb_hist)
                       const uint32_t* bsum = nullptr,  // with it: F1's scanned block sums -- the
                                                          // placement writes `offsets` itself
@@ -84,11 +84,11 @@ int launch_rb_binning(const uint32_t* tiles, uint4* rect, uint32_t* offsets, int
                       uint2* tpair = nullptr);              // and the instances to tpair as (gid, key), not tgid
 
 // Per-tile depth order: every tile's slice of `gid` (tile-sorted, gid order within a tile) is
-// sorted in place by (depth_key[gid], gid) -- the canonical (tile, depth, gid) order -- with a
-// stable LDS radix sort of the depth keys.  Slices longer than the first kernel's LDS form are
-// queued in `ovf` (count at *ovf_count, zeroed) for 8192-entry blocks, longer ones again in
-// ovf2 for a global-memory form using scratch_hi / scratch_lo (K u32 each, free after the tile
-// sort).  K: the binning's capacity (it sizes the LDS form from the mean slice).
+// sorted in place by (depth_key[gid], gid) -- the canonical (tile, depth, gid) order.  Slices
+// longer than the first kernel's form are queued in `ovf` (count at *ovf_count, zeroed) for the
+// next one, longer ones again in ovf2 for tile_depth_sort_big (LDS radix sort of up to 16384
+// entries; beyond that a global-memory merge using scratch_hi / scratch_lo, K u32 each, free
+// after the tile sort).  K: the binning's capacity (the mean slice picks the first form).
 // Presort mode (gsr_internal.h use_presort): the P depth keys sorted (stable, gid values), then
 // each rank's (tiles, rect, gid) gathered into rank order with its 256-rank block's tiles_touched
 // sum in bsum (div_up(n, 256) words), which are then scanned in place (exclusive) with the total
@@ -101,9 +101,10 @@ int launch_depth_presort(const uint32_t* depth_key, const uint32_t* tiles, const
 int launch_duplicate_ranked(const uint32_t* rtiles, const uint4* rrect, uint4* rect, int n, int grid_x, int ty0,
                             const uint32_t* bexcl, uint32_t* offsets, uint32_t* tkey, uint32_t* tgid, long long cap,
                             hipStream_t s);
-// Mean slices of up to ~1365 entries use the register form instead (one wave per slice of <= 1024
-// entries, a 2048-entry wave for the queued longer ones where the mean is near 1024; the rest
-// through the 1024-thread LDS form of tile_depth_sort_big).
+// Mean slices of up to ~1365 entries: one wave per slice of <= 1024 entries, in registers (a
+// 2048-entry wave for the queued longer ones where the mean is near 1024).  Deeper means: one
+// block of 4 waves per tile and an 8-wave queue, or 8 waves at once on launches of fewer than
+// GSR_BLOCK8_TILES tiles.
 int launch_tile_depth_sort(const uint2* ranges, int tile0, int ntiles, long long K, const uint32_t* depth_key,
                            uint32_t* gid, uint32_t* ovf, uint32_t* ovf_count, uint32_t* ovf2, uint32_t* ovf2_count,
                            uint32_t* done, uint32_t* scratch_hi, uint32_t* scratch_lo, hipStream_t s,
@@ -112,9 +113,8 @@ int launch_tile_depth_sort(const uint2* ranges, int tile0, int ntiles, long long
 // the sort reads them coalesced, instead of gathering depth_key[gid], and writes the ordered gids
 // to `gid` (the forms that sort in place get their slices' gids copied there first).
 // unordered: the tiles' entries are in arbitrary order (row-bucketed binning), not gid order --
-// the register form needs nothing else; the LDS forms then also sort by gid (LSD, gid passes first).
-// True when the register form takes the mean slice (the row-bucketed binning is used only then).
-bool tile_wave_sort_eligible(long long K, int ntiles);
+// the register forms need nothing else; tile_depth_sort_big then also puts runs of equal depth keys
+// into gid order.
 
 // F5: ranges[tile] = [start, end) of the sorted tile keys (K = min(*K_dev, cap))
 int launch_tile_keys_from_ranges(const uint2* ranges, int tiles, long long cap, uint32_t* tkey, hipStream_t s);
@@ -158,11 +158,7 @@ int launch_blend_backward(const gsr_camera& cam, const float bg[3], int ty0, int
                           const float4* rec, const float* final_T,
                           const float* accum, const float* dL_dpix, float* partial, long long cap,
                           const uint32_t* term, const float4* ck, hipStream_t s, int vgy = 0, int vh = 0,
-                          const uint8_t* mk = nullptr, int split = 1);
-// B1 parts per (tile, chunk) for a launch over tile rows [ty0, ty1) (views mode: vgy rows per
-// view): 1 on full images, GSR_B1_BAND_SPLIT on band launches; the partial block then holds
-// cap * split entries (entry j * split + part) and the gather sums them (launch_gather_grad2d)
-int b1_split(int W, int H, int ty0, int ty1, int vgy);
+                          const uint8_t* mk = nullptr);
 // (vgy, vh: views mode -- bands of vgy tile rows per view, vh valid pixel rows each; 0 = one image)
 
 // record layout constants shared by preprocess and the blend kernels
@@ -172,7 +168,7 @@ constexpr float kLn2 = 0.6931471805599453f;  // conic A = -2 ln2 a', B = -ln2 b'
 // culled Gaussians).  offsets: the inclusive tile scan in gid order; partial: PartLayout(cap).
 // rrect: the rank-order payload in presort mode (offsets then in rank order), else nullptr
 int launch_gather_grad2d(const uint32_t* offsets, const float* partial, const float4* rec, int W, int H,
-                         long long cap, int P, const uint4* rrect, float* grad2d, hipStream_t s, int split = 1,
+                         long long cap, int P, const uint4* rrect, float* grad2d, hipStream_t s,
                          bool aux = false);  // aux: partial is PartLayout(cap, true); its pz sums go to slot 9
 
 struct GradOut {

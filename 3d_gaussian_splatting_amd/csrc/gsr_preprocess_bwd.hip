@@ -38,12 +38,6 @@ constexpr float kC1 = 0.4886025119029199f;
 // conversion runs once on the per-Gaussian sum, with the Gaussian's own conic and opacity from
 // its blend record.  The 48-B result lands at grad2d[gid].
 constexpr int kGatherWin = 512;
-#ifndef GSR_GATHER_FLAG_AHEAD
-#define GSR_GATHER_FLAG_AHEAD 1
-#endif
-#ifndef GSR_GATHER_DATA_AHEAD
-#define GSR_GATHER_DATA_AHEAD 1
-#endif
 
 // rrect (presort mode): index i is a depth rank whose emission range the rank-order offsets give;
 // its Gaussian (record read, grad2d row written) is rrect[i].z.  nullptr: i is the gid itself.
@@ -60,22 +54,18 @@ __global__ __launch_bounds__(256) void gather_grad2d_kernel(const uint32_t* __re
                                                             const uint8_t* __restrict__ fl,
                                                             const float4* __restrict__ rec, float hw, float hh,
                                                             int P, uint32_t cap, const uint4* __restrict__ rrect,
-                                                            float* __restrict__ grad2d, uint32_t split,
-                                                            const PZ... pzp) {
+                                                            float* __restrict__ grad2d, const PZ... pzp) {
     constexpr bool AUX = sizeof...(PZ) > 0;
     static_assert(sizeof...(PZ) <= 1, "one aux argument");
-    static_assert(!AUX || GSR_GATHER_DATA_AHEAD, "the aux gather is written for GSR_GATHER_DATA_AHEAD");
     const float* __restrict__ pz = gather_pz(pzp...);
     __shared__ float4 w8[2 * kGatherWin];
     __shared__ float w1[kGatherWin];
     __shared__ float wz[AUX ? kGatherWin : 1];
     float az = 0.f;
-    __shared__ uint32_t wv[kGatherWin / 4];
     const int g0 = blockIdx.x * 256, g = g0 + threadIdx.x;
     const int gl = (P - g0 < 256 ? P - g0 : 256) + g0;  // one past the block's last Gaussian
-    // emission indices past the binning's capacity were never emitted (overflow): clamped; a
-    // split B1 (band launches) wrote `split` consecutive entries per instance, summed in order
-    auto off = [&](int i) { const uint32_t o = offsets[i]; return (o < cap ? o : cap) * split; };
+    // emission indices past the binning's capacity were never emitted (overflow): clamped
+    auto off = [&](int i) { const uint32_t o = offsets[i]; return o < cap ? o : cap; };
     const uint32_t J0 = g0 ? off(g0 - 1) : 0u, J1 = off(gl - 1);
     const uint32_t s = g < P ? (g ? off(g - 1) : 0u) : 0u;
     const uint32_t e = g < P ? off(g) : 0u;
@@ -89,14 +79,11 @@ __global__ __launch_bounds__(256) void gather_grad2d_kernel(const uint32_t* __re
     float a[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) a[k] = 0.f;
-    const uint8_t* wvb = reinterpret_cast<const uint8_t*>(wv);
-#if GSR_GATHER_DATA_AHEAD
     // Each window's entries are loaded into registers during the previous window's sums (4 float4 +
     // 2 floats per thread), and its flags a window earlier still (double-buffered in LDS): after
     // the first window no window waits on a load round at all.
     static_assert(kGatherWin == 512, "two entries per thread");
     __shared__ uint32_t wvd[2][kGatherWin / 4];
-    (void)wvb;
     auto nwin = [&](uint32_t W) -> uint32_t {
         return W < J1 ? (J1 - W < (uint32_t)kGatherWin ? J1 - W : (uint32_t)kGatherWin) : 0u;
     };
@@ -165,48 +152,6 @@ __global__ __launch_bounds__(256) void gather_grad2d_kernel(const uint32_t* __re
         }
         __syncthreads();
     }
-#else
-#if GSR_GATHER_FLAG_AHEAD
-    // each window's flags are loaded during the previous window's entry loads (two per thread in
-    // registers), so a window waits for one load round, not two
-    static_assert(kGatherWin == 512, "two flags per thread");
-    uint32_t fa = 0u, fb = 0u;
-    {
-        const uint32_t n0 = J1 - J0 < (uint32_t)kGatherWin ? J1 - J0 : (uint32_t)kGatherWin;
-        if (threadIdx.x < n0) fa = fl[(size_t)J0 + threadIdx.x];
-        if (threadIdx.x + 256 < n0) fb = fl[(size_t)J0 + threadIdx.x + 256];
-    }
-#endif
-    for (uint32_t W = J0; W < J1; W += kGatherWin) {
-        const uint32_t n = J1 - W < (uint32_t)kGatherWin ? J1 - W : (uint32_t)kGatherWin;
-#if GSR_GATHER_FLAG_AHEAD
-        if (threadIdx.x < n) reinterpret_cast<uint8_t*>(wv)[threadIdx.x] = (uint8_t)fa;
-        if (threadIdx.x + 256 < n) reinterpret_cast<uint8_t*>(wv)[threadIdx.x + 256] = (uint8_t)fb;
-        __syncthreads();
-        {
-            const uint32_t W2 = W + kGatherWin;
-            const uint32_t n2 = W2 < J1 ? (J1 - W2 < (uint32_t)kGatherWin ? J1 - W2 : (uint32_t)kGatherWin) : 0u;
-            fa = threadIdx.x < n2 ? fl[(size_t)W2 + threadIdx.x] : 0u;
-            fb = threadIdx.x + 256 < n2 ? fl[(size_t)W2 + threadIdx.x + 256] : 0u;
-        }
-#else
-        for (uint32_t i = threadIdx.x; i < n; i += 256) reinterpret_cast<uint8_t*>(wv)[i] = fl[(size_t)W + i];
-        __syncthreads();
-#endif
-        for (uint32_t i = threadIdx.x; i < 2 * n; i += 256)
-            w8[i] = wvb[i >> 1] ? p8[2 * (size_t)W + i] : make_float4(0.f, 0.f, 0.f, 0.f);
-        for (uint32_t i = threadIdx.x; i < n; i += 256) w1[i] = wvb[i] ? p1[(size_t)W + i] : 0.f;
-        __syncthreads();
-        const uint32_t lo = s > W ? s : W, hi = e < W + n ? e : W + n;
-        for (uint32_t j = lo; j < hi; ++j) {
-            const float4 u = w8[2 * (j - W)], v = w8[2 * (j - W) + 1];
-            a[0] += u.x; a[1] += u.y; a[2] += u.z; a[3] += u.w;
-            a[4] += v.x; a[5] += v.y; a[6] += v.z; a[7] += v.w;
-            a[8] += w1[j - W];
-        }
-        __syncthreads();
-    }
-#endif
     if (g >= P) return;
     // moments -> d mean2D (NDC), d conic, d opacity (sum G dL/dalpha = S0 / o), d colour
     const float A = -2.0f * kLn2 * q0.z, B = -kLn2 * q0.w, C = -2.0f * kLn2 * q1.x;
@@ -575,10 +520,6 @@ __device__ __forceinline__ void preprocess_backward_one(const gsr_camera& cam, c
     out.rots[4 * o + 3] = 2.f * (-2.f * z * dR[0] - r * dR[1] + x * dR[2] + r * dR[3] - 2.f * z * dR[4] + y * dR[5] + x * dR[6] + y * dR[7]);
 }
 
-#ifndef GSR_B2_VEC4
-#define GSR_B2_VEC4 1
-#endif
-
 // Gaussians [g0, g0 + n): inputs indexed by g, grad2d and every output by o = g - g0.
 // view v's leaf outputs: `out` for v = 0, slice v - 1 of `scratch`; its 2D gradients: rows v * P..
 __device__ __forceinline__ GradOut view_out(const GradOut& out, const GradOut& scratch, int v, size_t P, int M3) {
@@ -622,8 +563,8 @@ __global__ __launch_bounds__(256) void preprocess_backward_kernel(
     const size_t obase = (size_t)blockIdx.x * 256 * M3, ibase = (size_t)g0 * M3 + obase;
     // 16-B staging when the rows start 16-B aligned (always for g0 = 0: a block's 256 rows are
     // 46080 B); 4-B otherwise
-    const bool v4 = GSR_B2_VEC4 && ((reinterpret_cast<uintptr_t>(in.sh_rest + ibase) |
-                                     reinterpret_cast<uintptr_t>(out.sh_rest + obase)) & 15u) == 0;
+    const bool v4 = ((reinterpret_cast<uintptr_t>(in.sh_rest + ibase) |
+                      reinterpret_cast<uintptr_t>(out.sh_rest + obase)) & 15u) == 0;
     // Aligned rows are staged by buffer-load-to-LDS DMA: the block's 256 * M3 floats are M3 pieces
     // of 1 KB (64 lanes x 16 B), piece q by wave q % 4, all issued before the per-Gaussian inputs
     // (loads return in order: one wait covers both); the piece offset is in voffset, which the
@@ -668,21 +609,20 @@ __global__ __launch_bounds__(256) void preprocess_backward_kernel(
 }  // namespace
 
 int launch_gather_grad2d(const uint32_t* offsets, const float* partial, const float4* rec, int W, int H,
-                         long long cap, int P, const uint4* rrect, float* grad2d, hipStream_t s, int split, bool aux) {
+                         long long cap, int P, const uint4* rrect, float* grad2d, hipStream_t s, bool aux) {
     if (P <= 0) return 0;
-    const PartLayout pl(cap * split, aux);
+    const PartLayout pl(cap, aux);
     const char* base = reinterpret_cast<const char*>(partial);
     if (aux)
         hipLaunchKernelGGL(gather_grad2d_kernel<const float*>, dim3(div_up(P, 256)), dim3(256), 0, s, offsets,
                            reinterpret_cast<const float4*>(base + pl.p8), reinterpret_cast<const float*>(base + pl.p1),
                            reinterpret_cast<const uint8_t*>(base + pl.fl), rec, 0.5f * (float)W, 0.5f * (float)H, P,
-                           (uint32_t)cap, rrect, grad2d, (uint32_t)split,
-                           reinterpret_cast<const float*>(base + pl.pz));
+                           (uint32_t)cap, rrect, grad2d, reinterpret_cast<const float*>(base + pl.pz));
     else
         hipLaunchKernelGGL(gather_grad2d_kernel<>, dim3(div_up(P, 256)), dim3(256), 0, s, offsets,
                            reinterpret_cast<const float4*>(base + pl.p8), reinterpret_cast<const float*>(base + pl.p1),
                            reinterpret_cast<const uint8_t*>(base + pl.fl), rec, 0.5f * (float)W, 0.5f * (float)H, P,
-                           (uint32_t)cap, rrect, grad2d, (uint32_t)split);
+                           (uint32_t)cap, rrect, grad2d);
     return (int)hipGetLastError();
 }
 

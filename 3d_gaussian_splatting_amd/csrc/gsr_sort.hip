@@ -32,7 +32,6 @@ namespace {
 constexpr int kB = kSortBlock;       // 256 threads = 4 waves
 constexpr int kI = kSortItems;       // 16 rounds per wave
 constexpr int kWaves = kB / 64;
-constexpr int kWaveItems = kI * 64;  // 1024 contiguous items per wave
 
 __device__ inline uint64_t lanemask_lt() {
     const int lane = threadIdx.x & 63;
@@ -303,33 +302,10 @@ __global__ __launch_bounds__(kB) void scan_reduce(const uint32_t* __restrict__ i
 
 // Exclusive scan of n words in place by one block of 1024 threads, kScanQ contiguous words per
 // thread per round (all of a round's loads issued before its block scan): one load latency and
-// one block scan per 8192 words, not per 1024 (the F2 block sums at 5M: 19.5k words).
-// Up to kScanQ1 x 1024 words (5M: 19.5k) in one round: Q = ceil(n / 1024) consecutive words per
-// thread, one load latency, one block scan, one store pass (three serial rounds of 8192 took
-// ~7 us each at 5M).
-#ifndef GSR_SCAN_ONE_ROUND
-#define GSR_SCAN_ONE_ROUND 1
-#endif
+// one block scan per 8192 words, not per 1024.  The form for rows past kScanQ1 x 1024 words;
+// shorter rows take wide_block_scan_lds.
 constexpr int kScanQ = 8, kScanQ1 = 32;
 __device__ __forceinline__ uint32_t wide_block_scan(uint32_t* __restrict__ a, int n, uint32_t* wsum) {
-    if (GSR_SCAN_ONE_ROUND && n <= 1024 * kScanQ1) {
-        const int Q = (n + 1023) / 1024;
-        const int i0 = (int)threadIdx.x * Q;
-        uint32_t v[kScanQ1], sv = 0;
-#pragma unroll
-        for (int q = 0; q < kScanQ1; ++q) {
-            v[q] = q < Q && i0 + q < n ? a[i0 + q] : 0u;
-            sv += v[q];
-        }
-        uint32_t tot;
-        uint32_t run = block_exclusive_scan(sv, wsum, &tot);
-#pragma unroll
-        for (int q = 0; q < kScanQ1; ++q) {
-            if (q < Q && i0 + q < n) a[i0 + q] = run;
-            run += v[q];
-        }
-        return tot;
-    }
     uint32_t carry = 0;
     for (int base = 0; base < n; base += 1024 * kScanQ) {
         const int i0 = base + (int)threadIdx.x * kScanQ;
@@ -351,13 +327,12 @@ __device__ __forceinline__ uint32_t wide_block_scan(uint32_t* __restrict__ a, in
     return carry;
 }
 
-// The single-round scan through LDS (dynamic LDS of n words, n <= kScanQ1 x 1024): the array is
-// loaded and stored coalesced (word i by thread i mod 1024), and each thread scans its Q
-// consecutive words out of LDS -- the direct form's loads of Q consecutive words per thread touch
-// a different cache line in every lane of every load instruction.
-#ifndef GSR_SCAN_LDS
-#define GSR_SCAN_LDS 1
-#endif
+// Up to kScanQ1 x 1024 words (the F2 block sums at 5M: 19.5k) in one round through LDS (dynamic
+// LDS of n words): Q = ceil(n / 1024) consecutive words per thread, one load latency, one block
+// scan, one store pass (three serial rounds of 8192 took ~7 us each at 5M).  The array is loaded
+// and stored coalesced (word i by thread i mod 1024), and each thread scans its Q consecutive
+// words out of LDS -- loads of Q consecutive words per thread straight from memory touch a
+// different cache line in every lane of every load instruction.
 __device__ __forceinline__ uint32_t wide_block_scan_lds(uint32_t* __restrict__ a, int n, uint32_t* wsum,
                                                         uint32_t* buf) {
     for (int i = (int)threadIdx.x; i < n; i += 1024) buf[i] = a[i];
@@ -381,7 +356,7 @@ __device__ __forceinline__ uint32_t wide_block_scan_lds(uint32_t* __restrict__ a
     for (int i = (int)threadIdx.x; i < n; i += 1024) a[i] = buf[i];
     return tot;
 }
-__host__ __device__ constexpr bool scan_lds_fits(long long n) { return GSR_SCAN_LDS && n <= 1024LL * kScanQ1; }
+__host__ __device__ constexpr bool scan_lds_fits(long long n) { return n <= 1024LL * kScanQ1; }
 
 // exclusive scan of the nb block totals in place; the grand total to *total_out
 __global__ __launch_bounds__(1024) void scan_partials(uint32_t* __restrict__ partials, int nb,
@@ -685,31 +660,21 @@ __global__ __launch_bounds__(256) void rank_payload_kernel(const uint32_t* __res
 //      row's [column][chunk] counts scanned flat with a look-back over rows (rb_tiles_scan, which
 //      also writes the tile ranges), and each chunk's instances placed from LDS column counters,
 //      staged in LDS and written as coalesced column runs (rb_chunks_place).
-// Result: every tile's entries contiguous, the ranges F5 would write, the tile keys -- ~140 MB of
+// Result: every tile's entries contiguous and the ranges F5 would write -- ~140 MB of
 // traffic and no separate F3 / F5 -- but a tile's entries in arbitrary order: the per-tile depth
-// sort that follows orders them by the whole (depth, gid) key (the register form; the LDS forms
-// add gid passes, `unordered`), so the canonical list is the radix path's bit for bit.  Used when
+// sort that follows orders them by the whole (depth, gid) key (the register forms; with
+// `unordered` tile_depth_sort_big puts its depth ties in gid order), so the canonical list is the
+// radix path's bit for bit.  Used when
 // the image has at most kRbMaxRows tile rows and kRbMaxCols tile columns (row / column ids fit one
 // byte; tall grids of at most kRbMaxRows tile rows -- views mode's stacked images included -- take
 // it too), outside presort mode, below kRbMaxCap instances (gsr_api.cpp expected_layout; recorded
 // in gsr_buffers.layout).
 constexpr int kRbChunk = kRbChunkPairs;  // pairs per pass-B block (4 per thread)
-// GSR_RB_STAGE32 1: pass B stages (pair index | column << 16) as one word per instance (no
-// sub-dword LDS stores from neighbouring lanes into one dword)
-#ifndef GSR_RB_STAGE32
-#define GSR_RB_STAGE32 1
-#endif
 static_assert(kRbChunk % 256 == 0 && kRbMaxRows == 256 && kRbMaxCols == 256, "one row / column per thread");
-#ifndef GSR_RB_STAGE_A
-#define GSR_RB_STAGE_A 1024
-#endif
 // LDS staging (pairs) of a pass-A block (~720 at 1M / 1080p; a block past it writes unstaged):
 // 1024 keeps the block at 16 KB, 8 waves per SIMD (2048: 30 KB, 5)
-constexpr int kRbStageA = GSR_RB_STAGE_A;
-#ifndef GSR_RB_STAGE_B
-#define GSR_RB_STAGE_B 4096
-#endif
-constexpr int kRbStage = GSR_RB_STAGE_B;  // LDS staging (instances) of a pass-B block (~2800 at 1M / 1080p)
+constexpr int kRbStageA = 1024;
+constexpr int kRbStage = 4096;  // LDS staging (instances) of a pass-B block (~2800 at 1M / 1080p)
 constexpr uint32_t kRbAgg = 1u << 30, kRbInc = 2u << 30, kRbCntMask = kRbAgg - 1u;
 
 // rows of one block's Gaussians -> histA[r * nbA + b] (F1 writes the same counts itself when it
@@ -953,7 +918,7 @@ __global__ __launch_bounds__(kRbScanThreads) void rb_tiles_scan(const uint32_t* 
     // the common case: the partition's counts in registers, Q consecutive ones per thread (up to
     // kRbScanQ x 1024), one block scan and one write of the final positions
     const uint32_t Q = (E + kRbScanThreads - 1) / kRbScanThreads;
-    const bool one = Q <= (uint32_t)(GSR_SCAN_ONE_ROUND ? kRbScanQ : 4);
+    const bool one = Q <= (uint32_t)kRbScanQ;
     const uint32_t i0 = Q * tid;
     uint32_t cnts[kRbScanQ], excl = 0, carry = 0;
     if (one) {
@@ -1047,18 +1012,16 @@ __global__ __launch_bounds__(kRbScanThreads) void rb_tiles_scan(const uint32_t* 
 
 // pass B, placement: each chunk's instances, a slot per instance from its column's LDS counter
 // (order inside a tile is free, as in pass A), staged in LDS by column and written as coalesced
-// column runs (tile key and gid; with tpair the (gid, depth key) pair, the key from pass A's
+// column runs (the gid; with tpair the (gid, depth key) pair, the key from pass A's
 // ppair, so the per-tile sort that follows reads its keys coalesced instead of gathering one
 // behind every gid load, one 8-B store per instance).  The staging holds each instance's pair
-// index (u16) and column; the chunk's pairs (gid, key) sit in LDS beside it.
-#ifndef GSR_RB_PLACE_WPE
-#define GSR_RB_PLACE_WPE 1
-#endif
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GSR_RB_PLACE_WPE))) void rb_chunks_place(const uint32_t* __restrict__ pgid, const uint32_t* __restrict__ pxr,
-                                                       const uint32_t* __restrict__ totA, int R, int gx, int ty0,
+// index (16 bits) and column; the chunk's pairs (gid, key) sit in LDS beside it.
+constexpr int kRbPlaceWpe = 1;
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kRbPlaceWpe))) void rb_chunks_place(const uint32_t* __restrict__ pgid, const uint32_t* __restrict__ pxr,
+                                                       const uint32_t* __restrict__ totA, int R, int gx,
                                                        long long pcap, long long cap,
                                                        const uint32_t* __restrict__ histB,
-                                                       uint32_t* __restrict__ tkey, uint32_t* __restrict__ tgid,
+                                                       uint32_t* __restrict__ tgid,
                                                        const uint2* __restrict__ ppair,
                                                        uint2* __restrict__ tpair) {
     __shared__ RbRows t;
@@ -1066,12 +1029,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GSR_RB_PLAC
     __shared__ uint32_t lb[kRbMaxCols];   // staging start of column c
     __shared__ uint32_t gb[kRbMaxCols];   // global position of the chunk's first instance of column c
     __shared__ uint32_t pg[kRbChunk], pk[kRbChunk];  // the chunk's pairs: gid, depth key
-#if GSR_RB_STAGE32
-    __shared__ uint32_t spc[kRbStage];                // staged instance: pair index | column << 16
-#else
-    __shared__ uint16_t sp[kRbStage];                 // staged instance: its pair (index in the chunk)
-    __shared__ uint8_t sc[kRbStage];
-#endif
+    // staged instance: pair index | column << 16, one word per instance (no sub-dword LDS stores
+    // from neighbouring lanes into one dword)
+    __shared__ uint32_t spc[kRbStage];
     __shared__ uint32_t wsum[kWaves];
     static_assert(kRbChunk <= 65536, "u16 pair index");
     const int tid = threadIdx.x;
@@ -1123,7 +1083,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GSR_RB_PLAC
         }
         __syncthreads();
         const bool staged = tot <= (uint32_t)kRbStage;  // block-uniform
-        const uint32_t row_tile = (uint32_t)(ty0 + ch.r) * (uint32_t)gx;
         if (staged) {
 #pragma unroll
             for (int q = 0; q < kQ; ++q) {
@@ -1136,16 +1095,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GSR_RB_PLAC
             for (uint32_t c = xr[q] & 0xFFFFu; c < (xr[q] >> 16); ++c) {
                 const uint32_t k = atomicAdd(&cnt[c], 1u);
                 if (staged) {
-#if GSR_RB_STAGE32
                     spc[lb[c] + k] = (uint32_t)(q * 256 + tid) | (c << 16);
-#else
-                    sp[lb[c] + k] = (uint16_t)(q * 256 + tid);
-                    sc[lb[c] + k] = (uint8_t)c;
-#endif
                 } else {
                     const long long pos = (long long)gb[c] + k;
                     if (pos < cap) {
-                        if (tkey) tkey[pos] = row_tile + c;
                         if (keys) tpair[pos] = make_uint2(gg[q], kk[q]);
                         else tgid[pos] = gg[q];
                     }
@@ -1155,20 +1108,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GSR_RB_PLAC
         if (staged) {
             __syncthreads();
             for (int i = tid; i < (int)tot; i += 256) {
-#if GSR_RB_STAGE32
                 const uint32_t pc = spc[i];
                 const int c = (int)(pc >> 16);
-#else
-                const int c = sc[i];
-#endif
                 const long long pos = (long long)gb[c] + ((uint32_t)i - lb[c]);
                 if (pos < cap) {
-                    if (tkey) tkey[pos] = row_tile + (uint32_t)c;
-#if GSR_RB_STAGE32
                     const int pi = (int)(pc & 0xFFFFu);
-#else
-                    const int pi = sp[i];
-#endif
                     if (keys) tpair[pos] = make_uint2(pg[pi], pk[pi]);
                     else tgid[pos] = pg[pi];
                 }
@@ -1209,40 +1153,35 @@ __global__ __launch_bounds__(256) void finalize_kernel(const uint32_t* __restric
 }
 
 // ---- per-tile depth order (canonical (tile, depth bits, gid) without a global depth sort) ----
+// The register forms below (one wave, or one block of waves, per tile) take slices of up to 8192
+// entries; longer ones, and those they hand on, go to tile_depth_sort_big, whose whole-slice sort
+// is the LDS radix sort here.
 // After the stable tile-bits sort of instances emitted in gid order, each tile's slice holds
 // its Gaussians in gid order, so a stable LSD sort of the 32-bit depth keys alone gives
 // (depth, gid) order.  Each pass is ranked exactly as radix_downsweep ranks (wave64 ballot
 // peer match, per-wave digit counters, a digit-major block scan), in LDS: ~20 B of LDS traffic
 // per key per pass, against ~log2(n)^2 / 2 x 12 B for a bitonic network, which is
-// LDS-bandwidth-bound.  Passes whose digit is equal for every key of the slice are skipped, so
-// 9-bit digits need 3 passes for the <= 27 differing bits of a 0.2 .. 100 depth range.
-// Measured at 1M/1080p: 9-bit radix 0.098 ms, 8-bit 0.102 ms, bitonic 0.130 ms; the radix form
-// is latency-bound per block (dependent LDS counter updates per 64-key round, ~6 syncs per
-// pass), not by LDS bandwidth.
+// LDS-bandwidth-bound.  Passes whose digit is equal for every key of the slice are skipped.
+// The radix form is latency-bound per block (dependent LDS counter updates per 64-key round, ~6
+// syncs per pass), not by LDS bandwidth.
 // NT threads, I items per thread: CAP = NT * I keys; wave w owns the contiguous run
 // [w * 64 I, (w + 1) * 64 I) of the slice, ranked round by round in index order (stable).
 // One slice [rg.x, rg.y) of n <= NT * I entries, sorted by the whole block.  Ends with every
 // LDS access behind a barrier, so a block may call it again for another slice.
+
 // Runs of equal depth keys in a depth-sorted slice (skey, sval in LDS, n entries) into gid order.
 // The thread holding a run's first entry sorts the run by insertion when it is at most
 // kTieRunMax long (runs are disjoint, so no two threads touch the same entries); if any run is
 // longer, the whole slice goes through an all-ascending bitonic network on the 64-bit (depth,
 // gid) keys in place (a degenerate slice: many Gaussians at one depth).  Ends behind a barrier.
-// lo_bit > 0 (a truncated sort, radix_sort_slice): the slice was ordered by the key bits at and
-// above lo_bit only, so a run is a group of equal TRUNCATED keys, and it is insertion-sorted by the
-// whole (depth, gid) pair (lo_bit = 0: runs of equal keys, sorted by gid -- the same thing).
 constexpr int kTieRunMax = 32;
-// (A truncated sort that meets a long group -- clustered depths, thousands of keys within one
-// truncated step -- takes the bitonic fallback on the whole pair as well.  Re-sorting such a slice
-// on every bit from the registers instead was tried in round 6 and faulted on the GPU in the
-// clustered-depth parity test; it is not used.)
-__device__ __forceinline__ void tie_fixup(uint32_t* skey, uint32_t* sval, int n, int nt, int lo_bit = 0) {
+__device__ __forceinline__ void tie_fixup(uint32_t* skey, uint32_t* sval, int n, int nt) {
     int longrun = 0;
     for (int i = threadIdx.x; i + 1 < n; i += nt) {
-        const uint32_t k = skey[i] >> lo_bit;
-        if ((skey[i + 1] >> lo_bit) != k || (i > 0 && (skey[i - 1] >> lo_bit) == k)) continue;  // not a run start
+        const uint32_t k = skey[i];
+        if (skey[i + 1] != k || (i > 0 && skey[i - 1] == k)) continue;  // not a run start
         int e = i + 2;
-        while (e < n && (skey[e] >> lo_bit) == k && e - i <= kTieRunMax) ++e;
+        while (e < n && skey[e] == k && e - i <= kTieRunMax) ++e;
         if (e - i > kTieRunMax) {
             longrun = 1;
             continue;
@@ -1283,27 +1222,6 @@ __device__ __forceinline__ void tie_fixup(uint32_t* skey, uint32_t* sval, int n,
     }
 }
 
-// out of line for the register-heavy slice kernels (its few live values cross the call)
-__device__ __attribute__((noinline)) void tile_tie_fixup(uint32_t* skey, uint32_t* sval, int n, int nt, int lo_bit) {
-    tie_fixup(skey, sval, n, nt, lo_bit);
-}
-
-// Truncated passes (unordered slices only): the LSD passes cover the top slice_passes(cap) * DB
-// differing key bits and tie_fixup orders the groups of equal truncated keys by the whole
-// (depth, gid) pair -- at 5M / 1080p (~4000-entry slices, 25 differing depth bits) two 9-bit
-// passes instead of three leave ~3 % of the entries in groups of 2-3.  Longer slices keep more
-// bits (a 8192-entry slice 3 x 8, so its groups stay as short); the 16384-entry form keeps all.
-// GSR_SLICE_TRUNC 0: every differing bit everywhere.
-#ifndef GSR_SLICE_TRUNC
-#define GSR_SLICE_TRUNC 1
-#endif
-#ifndef GSR_SLICE_PASSES_8K
-#define GSR_SLICE_PASSES_8K 3
-#endif
-__host__ __device__ constexpr int slice_passes(int cap) {
-    return !GSR_SLICE_TRUNC ? 0 : cap <= 4096 ? 2 : cap <= 8192 ? GSR_SLICE_PASSES_8K : 0;
-}
-
 template <int NT, int I, int DB>
 struct SliceLds {
     uint32_t wcnt[NT / 64][1 << DB];
@@ -1313,7 +1231,7 @@ struct SliceLds {
     uint32_t sval[NT * I];
 };
 
-template <int NT, int I, int DB, bool kFixInline = false>
+template <int NT, int I, int DB>
 __device__ __forceinline__ void radix_sort_slice(const uint2 rg, const uint32_t* __restrict__ depth_key,
                                                  uint32_t* __restrict__ gid, SliceLds<NT, I, DB>& lds,
                                                  bool unordered = false) {
@@ -1368,16 +1286,12 @@ __device__ __forceinline__ void radix_sort_slice(const uint2 rg, const uint32_t*
     const uint64_t lt = lanemask_lt();
     // The (stable) depth passes alone: a gid-ordered slice ends in (depth, gid) order.  An
     // unordered one (the row-bucketed binning leaves a tile's entries in arbitrary order) ends in
-    // depth order with each run of equal depth keys in arbitrary gid order; tile_tie_fixup puts
+    // depth order with each run of equal depth keys in arbitrary gid order; tie_fixup puts
     // those runs in gid order afterwards (ties are rare and short: an LSD pass over the gid bits
-    // per 8-9 of them would cost as much as the depth passes again).  An unordered slice is also
-    // sorted on its top slice_passes * DB differing bits only (lo_bit): the fix-up then orders the
-    // groups of equal truncated keys by the whole pair.
+    // per 8-9 of them would cost as much as the depth passes again).
     const int hb = diff ? 31 - __clz(diff) : 0;  // the highest differing bit
-    constexpr int KB = slice_passes(NT * I) * DB;  // kept bits (0: all)
-    const int lo_bit = (unordered && KB > 0 && hb + 1 > KB) ? hb + 1 - KB : 0;
     bool ran = false;
-    for (int shift = lo_bit; shift < 32 && shift <= hb; shift += DB) {
+    for (int shift = 0; shift < 32 && shift <= hb; shift += DB) {
         if (((diff >> shift) & DMASK) == 0u) continue;  // block-uniform
         ran = true;
         for (int d = tid; d < NWV * BINS; d += NT) (&wcnt[0][0])[d] = 0u;
@@ -1461,8 +1375,7 @@ __device__ __forceinline__ void radix_sort_slice(const uint2 rg, const uint32_t*
             }
             __syncthreads();
         }
-        if constexpr (kFixInline) tie_fixup(skey, sval, n, NT, lo_bit);
-        else tile_tie_fixup(skey, sval, n, NT, lo_bit);
+        tie_fixup(skey, sval, n, NT);
         for (int i = tid; i < n; i += NT) gid[rg.x + i] = sval[i];
         __syncthreads();  // skey / sval / red[] are rewritten by the next slice
         return;
@@ -1486,9 +1399,6 @@ __device__ __forceinline__ void radix_sort_slice(const uint2 rg, const uint32_t*
 // histogram: ~log2(64 E)^2 / 2 compare-exchange stages of 5-6 VALU ops per key pair, against the
 // LDS radix form's dependent counter updates and ~6 barriers per pass (latency-bound per block).
 // "Flip" network (every merge ascending: its first stage pairs i with i ^ (k - 1), mirrored).
-#ifndef GSR_TILE_WAVE_SORT
-#define GSR_TILE_WAVE_SORT 1
-#endif
 
 // x from lane (lane ^ M) of the wave, M = 2^a - 1 (mirror stages) or 2^a (half cleaners)
 template <int M>
@@ -1793,10 +1703,6 @@ __device__ __forceinline__ void wave_sort_slice32(const uint2 rg, const uint32_t
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-#ifndef GSR_WAVE_KEY32
-#define GSR_WAVE_KEY32 1
-#endif
-
 // Four tiles per 256-thread block, one per wave; slices longer than 1024 entries go to `ovf`.
 __global__ __launch_bounds__(256) void tile_depth_wave(const uint2* __restrict__ ranges, int tile0, int ntiles,
                                                       const uint32_t* __restrict__ depth_key,
@@ -1818,19 +1724,11 @@ __global__ __launch_bounds__(256) void tile_depth_wave(const uint2* __restrict__
         if (n > 1 && lane == 0) ovf[atomicAdd(ovf_count, 1u)] = (uint32_t)tile;
         return;
     }
-    if (GSR_WAVE_KEY32) {
-        if (n <= 64) wave_sort_slice32<1>(rg, depth_key, gid, lane, xs, src);
-        else if (n <= 128) wave_sort_slice32<2>(rg, depth_key, gid, lane, xs, src);
-        else if (n <= 256) wave_sort_slice32<4>(rg, depth_key, gid, lane, xs, src);
-        else if (n <= 512) wave_sort_slice32<8>(rg, depth_key, gid, lane, xs, src);
-        else wave_sort_slice32<16>(rg, depth_key, gid, lane, xs, src);
-        return;
-    }
-    if (n <= 64) wave_sort_slice<1>(rg, depth_key, gid, lane, xs, src);
-    else if (n <= 128) wave_sort_slice<2>(rg, depth_key, gid, lane, xs, src);
-    else if (n <= 256) wave_sort_slice<4>(rg, depth_key, gid, lane, xs, src);
-    else if (n <= 512) wave_sort_slice<8>(rg, depth_key, gid, lane, xs, src);
-    else wave_sort_slice<16>(rg, depth_key, gid, lane, xs, src);
+    if (n <= 64) wave_sort_slice32<1>(rg, depth_key, gid, lane, xs, src);
+    else if (n <= 128) wave_sort_slice32<2>(rg, depth_key, gid, lane, xs, src);
+    else if (n <= 256) wave_sort_slice32<4>(rg, depth_key, gid, lane, xs, src);
+    else if (n <= 512) wave_sort_slice32<8>(rg, depth_key, gid, lane, xs, src);
+    else wave_sort_slice32<16>(rg, depth_key, gid, lane, xs, src);
 }
 
 // The queued slices of 1025 .. 2048 entries, one wave each (a kernel of its own: the 32-entry-per-
@@ -1875,10 +1773,7 @@ __global__ __launch_bounds__(256) void tile_depth_wave_queue(const uint2* __rest
 // hands the tile on (`false`) to the next queue, whose forms sort every bit.
 // E: entries per lane (16: 1024 per wave; 8: 512 per wave, twice the waves per slice and one more
 // level of LDS merges, for a shorter chain per block)
-#ifndef GSR_BLOCK_E
-#define GSR_BLOCK_E 16
-#endif
-constexpr int kBlkE = GSR_BLOCK_E;
+constexpr int kBlkE = 16;
 __host__ __device__ constexpr int blk_pad(int i) { return i + (i >> 5); }
 __host__ __device__ constexpr int ilog2c(int x) { return x <= 1 ? 0 : 1 + ilog2c(x >> 1); }
 constexpr int kBlkW = 4096 / (64 * kBlkE), kBlkQW = 8192 / (64 * kBlkE);  // waves: <= 4096 / <= 8192
@@ -2074,9 +1969,6 @@ __device__ __forceinline__ bool block_sort_slice(const uint2 rg, const uint32_t*
     return true;
 }
 
-#ifndef GSR_TILE_BLOCK_SORT
-#define GSR_TILE_BLOCK_SORT 1
-#endif
 // launches of fewer tiles (multi-GPU bands) sort every deep slice with the 8-wave form in one round
 #ifndef GSR_BLOCK8_TILES
 #define GSR_BLOCK8_TILES 4096
@@ -2132,48 +2024,6 @@ __global__ __launch_bounds__(64 * kBlkQW) void tile_depth_block_queue(const uint
     }
 }
 
-// One block per tile of the launch; slices longer than NT * I go to the queue `ovf`.
-template <int NT, int I, int DB>
-__global__ __launch_bounds__(NT) void tile_depth_radix(const uint2* __restrict__ ranges, int tile0,
-                                                      const uint32_t* __restrict__ depth_key,
-                                                      uint32_t* __restrict__ gid, uint32_t* __restrict__ ovf,
-                                                      uint32_t* __restrict__ ovf_count, int unordered) {
-    const int tile = tile0 + blockIdx.x;
-    const uint2 rg = ranges[tile];
-    const int n = (int)(rg.y - rg.x);
-    if (n <= 1) return;
-    if (n > NT * I) {
-        if (threadIdx.x == 0) ovf[atomicAdd(ovf_count, 1u)] = (uint32_t)tile;
-        return;
-    }
-    __shared__ SliceLds<NT, I, DB> lds;
-    radix_sort_slice<NT, I, DB>(rg, depth_key, gid, lds, unordered != 0);
-}
-
-// The queued (longer) slices: blocks walk the queue; slices longer than NT * I go on to the
-// second queue (ovf2), which the global-memory form drains.  The queue length is on the device,
-// so blocks past it exit at once.
-template <int NT, int I, int DB>
-__global__ __launch_bounds__(NT) void tile_depth_radix_queue(const uint2* __restrict__ ranges,
-                                                            const uint32_t* __restrict__ depth_key,
-                                                            uint32_t* __restrict__ gid,
-                                                            const uint32_t* __restrict__ ovf,
-                                                            const uint32_t* __restrict__ ovf_count,
-                                                            uint32_t* __restrict__ ovf2, uint32_t* __restrict__ ovf2_count,
-                                                            int unordered) {
-    __shared__ SliceLds<NT, I, DB> lds;
-    const uint32_t cnt = *ovf_count;
-    for (uint32_t q = blockIdx.x; q < cnt; q += gridDim.x) {
-        const uint32_t tile = ovf[q];
-        const uint2 rg = ranges[tile];
-        if ((int)(rg.y - rg.x) > NT * I) {
-            if (threadIdx.x == 0) ovf2[atomicAdd(ovf2_count, 1u)] = tile;
-            continue;  // block-uniform
-        }
-        radix_sort_slice<NT, I, DB>(rg, depth_key, gid, lds, unordered != 0);
-    }
-}
-
 // Slices of 8193 and more entries (dense tiles of training views): one kernel, 1024-thread
 // blocks, 8 work items per queued tile.  A slice of <= 16384 entries is sorted whole in LDS by
 // item 0 (~145 KB: gfx950 gives one workgroup up to 160 KiB).  A longer slice is cut into
@@ -2211,7 +2061,7 @@ __shared__ union BigLds {
 
 __device__ __attribute__((noinline)) void big_slice_sort(const uint2 rg, const uint32_t* __restrict__ depth_key,
                                                          uint32_t* __restrict__ gid, bool unordered) {
-    radix_sort_slice<1024, 16, 8, true>(rg, depth_key, gid, g_big.slice, unordered);
+    radix_sort_slice<1024, 16, 8>(rg, depth_key, gid, g_big.slice, unordered);
 }
 
 __device__ __attribute__((noinline)) void merge_sorted_chunks(const uint2 r, const uint32_t* __restrict__ depth_key,
@@ -2381,7 +2231,7 @@ int launch_block_offsets(const uint32_t* tiles, int n, const uint32_t* bsum, uin
 
 int launch_rb_binning(const uint32_t* tiles, uint4* rect, uint32_t* offsets, int n, int gx, int ty0, int ty1,
                       uint32_t* histA, uint32_t* histB, uint32_t* rb_status, uint32_t* pgid, uint32_t* pxr,
-                      uint32_t* tkey, uint32_t* tgid, uint2* ranges, long long cap, hipStream_t s,
+                      uint32_t* tgid, uint2* ranges, long long cap, hipStream_t s,
                       bool rows_counted, const uint32_t* bsum, uint32_t* K_dev, const uint32_t* depth_key,
                       uint2* ppair, uint2* tpair) {
     const int R = ty1 - ty0;
@@ -2405,8 +2255,8 @@ int launch_rb_binning(const uint32_t* tiles, uint4* rect, uint32_t* offsets, int
     G = G < 1 ? 1 : G > gx ? gx : G;
     hipLaunchKernelGGL(rb_tiles_scan, dim3(R * G), dim3(kRbScanThreads), 0, s, totA, R, gx, ty0, cap, cap, histB,
                        rb_status + 16, rb_status, ranges, K_dev, G);
-    hipLaunchKernelGGL(rb_chunks_place, dim3(gplace), dim3(256), 0, s, pgid, pxr, totA, R, gx, ty0, cap, cap, histB,
-                       tkey, tgid, ppair, tpair);
+    hipLaunchKernelGGL(rb_chunks_place, dim3(gplace), dim3(256), 0, s, pgid, pxr, totA, R, gx, cap, cap, histB,
+                       tgid, ppair, tpair);
     return (int)hipGetLastError();
 }
 
@@ -2449,14 +2299,7 @@ int launch_duplicate_ranked(const uint32_t* rtiles, const uint4* rrect, uint4* r
     return (int)hipGetLastError();
 }
 
-// the gids of placed (gid, depth key) pairs, for the forms that sort gid[] in place
-__global__ __launch_bounds__(256) void copy_pair_gids(const uint2* __restrict__ src, long long n,
-                                                      uint32_t* __restrict__ gid) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) gid[i] = src[i].x;
-}
-
-// the LDS slice capacity the per-tile sort picks for a mean slice of K / ntiles entries
+// the slice capacity the per-tile sort picks for a mean slice of K / ntiles entries
 static int tile_sort_cap(long long K, int ntiles) {
     const long long mean = ntiles > 0 ? K / ntiles : K;
     int cap = 1024;
@@ -2464,30 +2307,22 @@ static int tile_sort_cap(long long K, int ntiles) {
     return cap;
 }
 
-bool tile_wave_sort_eligible(long long K, int ntiles) { return GSR_TILE_WAVE_SORT && tile_sort_cap(K, ntiles) <= 2048; }
-
 int launch_tile_depth_sort(const uint2* ranges, int tile0, int ntiles, long long K, const uint32_t* depth_key,
                            uint32_t* gid, uint32_t* ovf, uint32_t* ovf_count, uint32_t* ovf2, uint32_t* ovf2_count,
                            uint32_t* done, uint32_t* scratch_hi, uint32_t* scratch_lo, hipStream_t s,
                            bool unordered, const uint2* src) {
     if (ntiles <= 0 || K <= 0) return 0;
     const int uo = unordered ? 1 : 0;
-    // one block per tile holding up to cap entries in LDS, a power of two >= 1.5x the mean slice
-    // (1024 .. 4096: <= 43 KB of LDS, 3 blocks per CU); longer slices queue for 512-thread blocks
-    // of up to 8192 (73 KB: 2 per CU) walking the queue, and beyond that for tile_depth_sort_big
-    // (one 8192-entry block per tile at 5M / 1080p: 0.89 ms with 512 threads, 0.79 with 1024,
-    // against 0.49 for 4096-entry blocks + the queue: 1 block per CU)
-    const int cap = tile_sort_cap(K, ntiles);
-    // slices of up to 1024 entries sorted in registers, one wave each, whenever the
-    // mean slice leaves most tiles within that (the longer ones queue for the LDS forms below)
-    if (tile_wave_sort_eligible(K, ntiles)) {
+    const int bgrid = ntiles < 256 ? ntiles : 256;  // tile_depth_sort_big's blocks walk its queue
+    // Mean slices of up to ~1365 entries (cap <= 2048): slices of up to 1024 entries sorted in
+    // registers, one wave each (the mean leaves most tiles within that).
+    if (tile_sort_cap(K, ntiles) <= 2048) {
         hipLaunchKernelGGL(tile_depth_wave, dim3(div_up(ntiles, 4)), dim3(256), 0, s, ranges, tile0, ntiles, depth_key,
                            gid, ovf, ovf_count, src);
         // the slices past one wave's 1024 entries: where the mean is near 1024 (bands), many -- a
         // 2048-entry wave each, the rest on to the LDS form; elsewhere few (none at 1M / 1080p) --
         // all straight to the 1024-thread LDS form, one launch instead of two more near-empty
         // ones (~5 us each)
-        const int bgrid = ntiles < 256 ? ntiles : 256;
         if (K / ntiles > 900) {
             const int wgrid = ntiles < 2048 ? div_up(ntiles, 4) : 512;
             hipLaunchKernelGGL(tile_depth_wave_queue, dim3(wgrid), dim3(256), 0, s, ranges, depth_key, gid, ovf,
@@ -2498,69 +2333,21 @@ int launch_tile_depth_sort(const uint2* ranges, int tile0, int ntiles, long long
             hipLaunchKernelGGL(tile_depth_sort_big, dim3(bgrid), dim3(1024), 0, s, ranges, depth_key, gid, ovf,
                                ovf_count, done, scratch_hi, scratch_lo, uo);
         }
-        return (int)hipGetLastError();
-    } else {
-#define GSR_TILE_RADIX(NT_, I_)                                                                       \
-    hipLaunchKernelGGL((tile_depth_radix<NT_, I_, 9>), dim3(ntiles), dim3(NT_), 0, s, ranges, tile0, depth_key, \
-                       gid, ovf, ovf_count, uo)
-#ifndef GSR_BAND_SORT_NT
-#define GSR_BAND_SORT_NT 512
-#endif
-// full images: 256-thread blocks, or 512 when the mean slice is long (cap 4096; 0 = that rule):
-// 5M / 1080p 0.550 -> 0.490 ms with 512, 1M / 1080p (cap 2048) 0.103 -> 0.111 ms, so per cap
-#ifndef GSR_FULL_SORT_NT
-#define GSR_FULL_SORT_NT 0
-#endif
-    if (src && !(GSR_TILE_BLOCK_SORT && cap == 4096)) {  // the radix forms sort in place: gids first
-        hipLaunchKernelGGL(copy_pair_gids, dim3(div_up(K, 256)), dim3(256), 0, s, src, K, gid);
-        src = nullptr;
-    }
-    if (GSR_TILE_BLOCK_SORT && cap == 4096 && ntiles < GSR_BLOCK8_TILES) {  // bands: 8 waves per tile
+    } else if (ntiles < GSR_BLOCK8_TILES) {  // deep slices, few tiles (bands): 8 waves per tile, one round
         hipLaunchKernelGGL(tile_depth_block<kBlkQW>, dim3(ntiles), dim3(64 * kBlkQW), 0, s, ranges, tile0, depth_key, gid, ovf2,
                            ovf2_count, src);
-        const int bgrid = ntiles < 256 ? ntiles : 256;
         hipLaunchKernelGGL(tile_depth_sort_big, dim3(bgrid), dim3(1024), 0, s, ranges, depth_key, gid, ovf2,
                            ovf2_count, done, scratch_hi, scratch_lo, uo);
-        return (int)hipGetLastError();
-    }
-    if (GSR_TILE_BLOCK_SORT && cap == 4096) {  // deep slices: the block form, then its 8192-entry queue
+    } else {  // deep slices: the 4-wave block form, then its 8192-entry queue
+        // (one 8192-entry block per tile at 5M / 1080p: 0.89 ms with 512 threads, 0.79 with 1024,
+        // against 0.49 for 4096-entry blocks + the queue: 1 block per CU)
         hipLaunchKernelGGL(tile_depth_block<kBlkW>, dim3(ntiles), dim3(64 * kBlkW), 0, s, ranges, tile0, depth_key, gid, ovf,
                            ovf_count, src);
         hipLaunchKernelGGL(tile_depth_block_queue, dim3(ntiles), dim3(64 * kBlkQW), 0, s, ranges, depth_key, gid, ovf,
                            ovf_count, ovf2, ovf2_count, src);
-        const int bgrid = ntiles < 256 ? ntiles : 256;
         hipLaunchKernelGGL(tile_depth_sort_big, dim3(bgrid), dim3(1024), 0, s, ranges, depth_key, gid, ovf2,
                            ovf2_count, done, scratch_hi, scratch_lo, uo);
-        return (int)hipGetLastError();
     }
-    if (ntiles < 4096 && GSR_BAND_SORT_NT == 512) {  // band launches: fewer tiles, wider blocks
-        if (cap == 1024) GSR_TILE_RADIX(512, 2);
-        else if (cap == 2048) GSR_TILE_RADIX(512, 4);
-        else GSR_TILE_RADIX(512, 8);
-    } else if (ntiles < 4096 && GSR_BAND_SORT_NT == 1024) {
-        if (cap == 1024) GSR_TILE_RADIX(1024, 1);
-        else if (cap == 2048) GSR_TILE_RADIX(1024, 2);
-        else GSR_TILE_RADIX(1024, 4);
-    } else if (GSR_FULL_SORT_NT == 512 || (GSR_FULL_SORT_NT == 0 && cap == 4096)) {
-        if (cap == 1024) GSR_TILE_RADIX(512, 2);
-        else if (cap == 2048) GSR_TILE_RADIX(512, 4);
-        else GSR_TILE_RADIX(512, 8);
-    } else if (GSR_FULL_SORT_NT == 1024) {
-        if (cap == 1024) GSR_TILE_RADIX(1024, 1);
-        else if (cap == 2048) GSR_TILE_RADIX(1024, 2);
-        else GSR_TILE_RADIX(1024, 4);
-    } else if (cap == 1024) GSR_TILE_RADIX(256, 4);
-    else if (cap == 2048) GSR_TILE_RADIX(256, 8);
-    else GSR_TILE_RADIX(256, 16);
-#undef GSR_TILE_RADIX
-    }
-    const int qgrid = ntiles < 512 ? ntiles : 512;
-    hipLaunchKernelGGL((tile_depth_radix_queue<512, 16, 8>), dim3(qgrid), dim3(512), 0, s, ranges, depth_key, gid, ovf,
-                       ovf_count, ovf2, ovf2_count, uo);
-    // slices beyond 8192: the 16384-entry LDS form and the chunked form (tile_depth_sort_big)
-    const int bgrid = ntiles < 256 ? ntiles : 256;
-    hipLaunchKernelGGL(tile_depth_sort_big, dim3(bgrid), dim3(1024), 0, s, ranges, depth_key, gid, ovf2, ovf2_count,
-                       done, scratch_hi, scratch_lo, uo);
     return (int)hipGetLastError();
 }
 

@@ -315,26 +315,15 @@ __device__ __forceinline__ bool guard_tripped(const uint32_t* k, uint32_t cap) {
 // step, so they should not displace the L2 / MALL lines the rasterizer reuses.  Measured in the
 // configs[4] loop (6M Gaussians, 1280x832, 4000 iterations): 89.8 vs 87.2 iters/s; two float4
 // columns per thread: 87.6 (profiles/r04_experiments/loop_ab_4k.txt).
-#ifndef GSR_ADAM_NT
-#define GSR_ADAM_NT 1
-#endif
 constexpr int kAdamBlock = 256, kAdamVec = 1, kAdamPerBlock = 4 * kAdamVec * kAdamBlock;
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float4 ld4(const float* p) {
-#if GSR_ADAM_NT
     const f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p));
     return make_float4(v.x, v.y, v.z, v.w);
-#else
-    return *reinterpret_cast<const float4*>(p);
-#endif
 }
 __device__ __forceinline__ void st4(float* p, float4 v) {
-#if GSR_ADAM_NT
     const f32x4 w = {v.x, v.y, v.z, v.w};
     __builtin_nontemporal_store(w, reinterpret_cast<f32x4*>(p));
-#else
-    *reinterpret_cast<float4*>(p) = v;
-#endif
 }
 
 __device__ __forceinline__ float adam_one(float& p, float g, float& m, float& v, float ss, float b2s, const AdamArgs& a) {

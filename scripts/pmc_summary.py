@@ -50,7 +50,8 @@ def load(dirs):
 
 # Dominant read pattern per kernel: "stream" (coalesced 16-B/lane: FETCH counts half the bytes)
 # or "gather" (random 16/48-B records per lane: one 64-B tally per request).
-GATHER_KERNELS = ("blend_forward_kernel", "blend_backward_kernel", "tile_depth_radix", "tile_depth_sort")
+GATHER_KERNELS = ("blend_forward_kernel", "blend_backward_kernel", "tile_depth_wave", "tile_depth_block",
+                  "tile_depth_sort")
 
 
 def fetch_pattern(kernel: str) -> str:
