@@ -26,7 +26,11 @@ ARCH = "gfx950"
 
 HIP_SOURCES = {
     "gsr_preprocess.hip": ["-ffp-contract=off"],
-    "gsr_sort.hip": [],
+    # integer work: the global radix sort, the binning (scans, duplicate, row-bucketed passes,
+    # tile ranges), the per-tile depth order
+    "gsr_radix.hip": [],
+    "gsr_binning.hip": [],
+    "gsr_tilesort.hip": [],
     # F6 and B1 must evaluate alpha / T identically; no SLP packing (it splits DPP-fused adds)
     "gsr_blend.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
     # recomputes the forward's SH clamp bits: must round exactly like gsr_preprocess.hip
@@ -148,7 +152,9 @@ def build_torch_ext(verbose: bool = False, force: bool = False) -> str:
 def build_variant(name: str, defines: list, verbose: bool = False, csrc: str | None = None) -> str:
     """An experimental build of libgsr_hip.so with extra -D flags into lib/variants/<name>/ (for
     A/B timing with `bench.py --lib`; the product library is build_hip's).  `csrc`: build from
-    another copy of the kernel sources (e.g. an earlier commit's, for a before / after A/B)."""
+    another copy of the kernel sources (e.g. an earlier commit's, for a before / after A/B): that
+    tree's own *.hip files and the two host files, whatever they were called then, each with its
+    HIP_SOURCES flags where the name is still known and none otherwise."""
     src_dir = csrc or CSRC
     out_dir = os.path.join(LIB, "variants", name)
     os.makedirs(out_dir, exist_ok=True)
@@ -156,7 +162,7 @@ def build_variant(name: str, defines: list, verbose: bool = False, csrc: str | N
     hipcc = _hipcc()
 
     def one(src_name):
-        flags = HIP_SOURCES[src_name]
+        flags = HIP_SOURCES.get(src_name, [])
         obj = os.path.join(out_dir, src_name + ".o")
         lang = ["-x", "hip"] if src_name.endswith(".cpp") else []
         cmd = [hipcc] + COMMON + flags + ["-D" + d for d in defines] + lang + ["-I" + src_dir, "-c",
@@ -166,7 +172,7 @@ def build_variant(name: str, defines: list, verbose: bool = False, csrc: str | N
             raise RuntimeError(f"hipcc failed for {src_name}:\n{r.stderr}")
         return obj
 
-    names = [n for n in HIP_SOURCES if os.path.exists(os.path.join(src_dir, n))]  # an older commit's sources
+    names = sorted(n for n in os.listdir(src_dir) if n.endswith(".hip") or n in ("gsr_api.cpp", "gsr_comm.cpp"))
     with cf.ThreadPoolExecutor(max_workers=min(8, len(names))) as ex:
         objs = list(ex.map(one, names))
     r = subprocess.run([hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", so] + objs + LINK_LIBS,

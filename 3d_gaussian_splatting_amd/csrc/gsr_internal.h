@@ -77,14 +77,14 @@ inline size_t sort_scratch_words(long long n) { return 256 * ((size_t)radix_bloc
 constexpr long long kPresortMin = GSR_PRESORT_MIN;
 constexpr long long kPresortPerTile = GSR_PRESORT_PER_TILE;
 constexpr int kMaxViews = 8;  // gsr_forward_views: views per call (= GSR_MAX_VIEWS)
-// Row-bucketed binning (gsr_sort.hip): images of at most kRbMaxRows x kRbMaxCols tiles outside
+// Row-bucketed binning (gsr_binning.hip): images of at most kRbMaxRows x kRbMaxCols tiles outside
 // presort mode; chunks of kRbChunkPairs (Gaussian, row) pairs in its second pass.
 // The placement writes no tile keys (the GSR_VIEW_SORTED_TILE accessor fills them from the ranges
 // when asked); where the tile-key arrays have room it writes every instance's depth key beside its
 // gid instead (gsr_api.cpp rb_keys), so the per-tile sort that follows reads its keys coalesced
 // instead of through a dependent depth_key[gid] gather per entry (round 6).
 constexpr int kRbMaxRows = 256, kRbMaxCols = 256, kRbChunkPairs = 1024;
-// the binning's row scan splits a row into at most this many column partitions (gsr_sort.hip)
+// the binning's row scan splits a row into at most this many column partitions (gsr_binning.hip)
 constexpr int kRbScanSplit = 16;
 constexpr long long kRbMaxCap = 1LL << 30;  // the look-back's 30-bit counts (rb_tiles_scan)
 // gsr_buffers.layout (set by the forward, checked by every later use of the buffers): the tag

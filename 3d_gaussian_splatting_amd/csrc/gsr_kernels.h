@@ -42,6 +42,7 @@ struct CamArg {
 // view); view v's outputs at entries v * P + g, its tiles / pixel rows offset into a tall image.
 int launch_preprocess_views(const gsr_camera* cams, int V, const GaussIn& in, const PreOut& out, hipStream_t s);
 
+// ---- gsr_radix.hip ----
 // LSD radix sort of (u32 key, u32 value) by key bits [0, nbits); vals_in == nullptr means the
 // identity permutation.  Ping-pongs between (k0,v0) and (k1,v1); returns in *which (0/1) where
 // the sorted data ended.  Launched for `cap` items; n_dev (nullable) holds the live count
@@ -50,6 +51,7 @@ int radix_sort(const uint32_t* keys_in, const uint32_t* vals_in, uint32_t* k0, u
                uint32_t* k1, uint32_t* v1, long long cap, const uint32_t* n_dev, int nbits, uint32_t* hist,
                int* which, hipStream_t s);
 
+// ---- gsr_binning.hip ----
 // F2: inclusive scan of tiles[0..n) (gid order) -> offsets and the total K -> *total_out
 // (device), as three kernels for n > kFusedScanMax (nothing to do below: the fused kernel of
 // launch_duplicate scans).  scan_partials_buf: sort_blocks(n) + 16 u32.
@@ -83,12 +85,6 @@ int launch_rb_binning(const uint32_t* tiles, uint4* rect, uint32_t* offsets, int
                       uint2* ppair = nullptr,               // (gid, depth key) (pgid unused; pxr any cap u32)
                       uint2* tpair = nullptr);              // and the instances to tpair as (gid, key), not tgid
 
-// Per-tile depth order: every tile's slice of `gid` (tile-sorted, gid order within a tile) is
-// sorted in place by (depth_key[gid], gid) -- the canonical (tile, depth, gid) order.  Slices
-// longer than the first kernel's form are queued in `ovf` (count at *ovf_count, zeroed) for the
-// next one, longer ones again in ovf2 for tile_depth_sort_big (LDS radix sort of up to 16384
-// entries; beyond that a global-memory merge using scratch_hi / scratch_lo, K u32 each, free
-// after the tile sort).  K: the binning's capacity (the mean slice picks the first form).
 // Presort mode (gsr_internal.h use_presort): the P depth keys sorted (stable, gid values), then
 // each rank's (tiles, rect, gid) gathered into rank order with its 256-rank block's tiles_touched
 // sum in bsum (div_up(n, 256) words), which are then scanned in place (exclusive) with the total
@@ -101,6 +97,19 @@ int launch_depth_presort(const uint32_t* depth_key, const uint32_t* tiles, const
 int launch_duplicate_ranked(const uint32_t* rtiles, const uint4* rrect, uint4* rect, int n, int grid_x, int ty0,
                             const uint32_t* bexcl, uint32_t* offsets, uint32_t* tkey, uint32_t* tgid, long long cap,
                             hipStream_t s);
+
+// F5: ranges[tile] = [start, end) of the sorted tile keys (K = min(*K_dev, cap))
+int launch_finalize(const uint32_t* sorted_tile, long long cap, const uint32_t* K_dev, uint2* ranges, hipStream_t s);
+// tile keys from the ranges (the row-bucketed binning writes none: for GSR_VIEW_SORTED_TILE)
+int launch_tile_keys_from_ranges(const uint2* ranges, int tiles, long long cap, uint32_t* tkey, hipStream_t s);
+
+// ---- gsr_tilesort.hip ----
+// Per-tile depth order: every tile's slice of `gid` (tile-sorted, gid order within a tile) is
+// sorted in place by (depth_key[gid], gid) -- the canonical (tile, depth, gid) order.  Slices
+// longer than the first kernel's form are queued in `ovf` (count at *ovf_count, zeroed) for the
+// next one, longer ones again in ovf2 for tile_depth_sort_big (LDS radix sort of up to 16384
+// entries; beyond that a global-memory merge using scratch_hi / scratch_lo, K u32 each, free
+// after the tile sort).  K: the binning's capacity (the mean slice picks the first form).
 // Mean slices of up to ~1365 entries: one wave per slice of <= 1024 entries, in registers (a
 // 2048-entry wave for the queued longer ones where the mean is near 1024).  Deeper means: one
 // block of 4 waves per tile and an 8-wave queue, or 8 waves at once on launches of fewer than
@@ -115,10 +124,6 @@ int launch_tile_depth_sort(const uint2* ranges, int tile0, int ntiles, long long
 // unordered: the tiles' entries are in arbitrary order (row-bucketed binning), not gid order --
 // the register forms need nothing else; tile_depth_sort_big then also puts runs of equal depth keys
 // into gid order.
-
-// F5: ranges[tile] = [start, end) of the sorted tile keys (K = min(*K_dev, cap))
-int launch_tile_keys_from_ranges(const uint2* ranges, int tiles, long long cap, uint32_t* tkey, hipStream_t s);
-int launch_finalize(const uint32_t* sorted_tile, long long cap, const uint32_t* K_dev, uint2* ranges, hipStream_t s);
 
 // F6: per-tile front-to-back blend -> colour, final T, colour sum without background, the
 // tile's termination index term[], the B1 chunk checkpoints (ck: the binning buffer's

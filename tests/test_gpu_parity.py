@@ -334,13 +334,17 @@ def test_reference_kat_inputs_through_f1(rast):
 
 
 def test_dense_tiles_sort_paths(rast, oracle):
-    """Tiles holding more instances than the per-tile depth sort's smaller forms take:
-    (a) 60k Gaussians on a 64x48 image (12 tiles, ~10^4 instances each) exercise the
-    16384-slot LDS tier beyond 8192; (b) a cluster of 6000 Gaussians in the middle of a
-    sparse 256x256 scene overflows a 1024-slot tile into the 8192-slot LDS form; (c) 200k
-    Gaussians on 64x48 push tiles past 32768 into the chunked global bitonic form (global
-    strides 32768 and 16384, LDS strides below).  Canonical order, ranges and outputs must
-    still match the oracle."""
+    """Tiles holding more instances than the per-tile depth sort's register forms take (all three
+    scenes go through the row-bucketed binning, so the slices arrive unordered), in the order run:
+    (c) 200k Gaussians on 64x48 push every tile past 32768: the 8-wave block form
+    (tile_depth_block<8>, few tiles) hands them all on to tile_depth_sort_big, which radix-sorts
+    16384-entry chunks in LDS and merges them (global strides 32768 and 16384, LDS strides below);
+    (a) 60k Gaussians on a 64x48 image (12 tiles, ~10^4 instances each): the block form sorts the
+    slices of up to 8192 entries and tile_depth_sort_big the longer ones whole in LDS (<= 16384);
+    (b) a cluster of 6000 Gaussians in the middle of a sparse 256x256 scene: the mean slice stays
+    below 1024, so the one-wave form (tile_depth_wave) sorts most tiles and queues the overflowing
+    ones (1025 .. 8192 entries) straight for tile_depth_sort_big.  Canonical order, ranges and
+    outputs must still match the oracle."""
     gr, sc = pkg("graphics"), pkg("scene")
     cam = gr.synthetic_camera(64, 48)
     s = sc.make_scene(cam, 200000, max_sh_degree=0, seed=15)
@@ -381,17 +385,20 @@ def test_dense_tiles_sort_paths(rast, oracle):
                                                 (1, 20000, 640, 360, False), (40, 20000, 640, 360, False)])
 def test_depth_ties_in_deep_tiles(levels, P, W, H, deep, rast, oracle):
     """Tiles whose Gaussians share a few depth values.  The row-bucketed binning hands the per-tile
-    sort each tile's entries in arbitrary order.  Deep tiles (thousands of entries: the LDS radix
-    forms) are sorted by depth alone and must notice the ties and order them by gid; shallow ones
-    (<= 1024: the register form on 32-bit keys) tie on their truncated keys and must do the same
-    (in place for short runs, by the 64-bit form for long ones), so that every list is the
-    canonical (depth, gid) one.  The synthetic camera has R = I, T = 0, so the view-space depth is
-    the world z exactly; levels = 1 puts every Gaussian at one depth.  levels = 0 keeps the
-    scene's continuous depths: the LDS forms sort deep slices on their top differing bits only
-    (two 9-bit passes at <= 4096 entries, three 8-bit ones at <= 8192) and order the groups of
-    equal truncated keys by the whole (depth, gid) pair -- P = 60000 puts most slices past 4096.
+    sort each tile's entries in arbitrary order.  Deep tiles (thousands of entries, 24 tiles: the
+    8-wave block form, tile_depth_block<8>, on 32-bit keys of the slice's top 19 differing depth
+    bits over the slice position) tie on their truncated keys: short runs are ordered in place from
+    the full (depth, gid) keys, a run past 16 hands the slice on to tile_depth_sort_big, whose LDS
+    radix sort orders by depth alone and must notice the ties and order them by gid (tie_fixup: by
+    insertion up to 32, else a 64-bit network over the slice).  Shallow ones (<= 1024: the one-wave
+    register form on 32-bit keys) tie on their truncated keys and must do the same (in place for
+    short runs, by the 64-bit form for long ones), so that every list is the canonical (depth, gid)
+    one.  The synthetic camera has R = I, T = 0, so the view-space depth is the world z exactly;
+    levels = 1 puts every Gaussian at one depth.  levels = 0 keeps the scene's continuous depths:
+    the block form's truncated keys tie in short runs only, and P = 60000 puts most slices past
+    4096 and some past the block form's 8192 (those go to tile_depth_sort_big whole).
     levels = -8: eight depth values, each Gaussian's a few ulps off its level, so the truncated
-    keys tie in groups of thousands that differ only below the kept bits (the long-group path)."""
+    keys tie in groups of thousands that differ only below the kept bits (the hand-on path)."""
     gr, sc = pkg("graphics"), pkg("scene")
     cam = gr.synthetic_camera(W, H)
     s = sc.make_scene(cam, P, max_sh_degree=1, seed=21)
