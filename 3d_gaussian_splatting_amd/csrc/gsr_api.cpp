@@ -201,6 +201,11 @@ void band(const gsr_camera* cam, const gsr_raster_settings* rs, int* y0, int* y1
     if (*y1 < *y0) *y1 = *y0;
 }
 
+// the settings' tile rows cover the whole image (band() then gives [0, gy))
+bool full_image(const gsr_camera* cam, const gsr_raster_settings* rs) {
+    return rs->tile_y0 <= 0 && rs->tile_y1 >= div_up(cam->height, kTile);
+}
+
 // Device pointers into the caller's buffers (layouts in gsr_internal.h).  n: Gaussians (or
 // received splat slots) indexed; cap: the binning's instance capacity.
 struct Views {
@@ -410,6 +415,11 @@ int fwd_phase2(FwdJob& j, long long cap, gsr_alloc_fn alloc_binning, void* ctx, 
     const bool scanned = use_rb_binning(j.n, j.gx, j.gy);  // phase 1 ran the three-kernel scan
     bufs->layout = expected_layout(j.n, j.gx, j.gy, cap) | j.aux_bits();
     const Views v = views(cam, j.n, bufs);
+    auto depth_sort = [&](bool unordered, const uint2* src) {
+        return launch_tile_depth_sort(v.ranges, j.ty0 * j.gx, ntiles, cap, v.depth_key, v.sorted_gid, v.ovf,
+                                      v.counters + kOvfCountSlot, v.ovf2, v.counters + kOvf2CountSlot, v.done,
+                                      v.free_k, v.free_v, stream, unordered, src);
+    };
     if (v.presort)
         GSR_STAGE(GSR_STAGE_DUPLICATE, launch_duplicate_ranked(v.rtiles, v.rrect, v.rect, (int)j.n, j.gx, j.ty0,
                                                                v.lookback, v.offsets, v.kA, v.vA, cap, stream),
@@ -440,11 +450,7 @@ int fwd_phase2(FwdJob& j, long long cap, gsr_alloc_fn alloc_binning, void* ctx, 
                                                          j.rows_counted ? v.lookback + 16 : nullptr, v.K_dev,
                                                          v.depth_key, ppair, tpair),
                   "row-bucketed binning");
-        GSR_STAGE(GSR_STAGE_DEPTH_SORT, launch_tile_depth_sort(v.ranges, j.ty0 * j.gx, ntiles, cap, v.depth_key,
-                                                               v.sorted_gid, v.ovf, v.counters + kOvfCountSlot, v.ovf2,
-                                                               v.counters + kOvf2CountSlot, v.done, v.free_k,
-                                                               v.free_v, stream, true, tpair),
-                  "per-tile depth order");
+        GSR_STAGE(GSR_STAGE_DEPTH_SORT, depth_sort(true, tpair), "per-tile depth order");
     } else if (cap > 0) {
         int which = -1;
         GSR_STAGE(GSR_STAGE_TILE_SORT, radix_sort(v.kA, v.vA, v.kB, v.vB, v.kA, v.vA, cap, v.K_dev, tile_bits(tiles),
@@ -454,26 +460,36 @@ int fwd_phase2(FwdJob& j, long long cap, gsr_alloc_fn alloc_binning, void* ctx, 
         if ((which == 0) != (v.sorted_tile == v.kB)) return fail(-12, "tile sort ended in an unexpected buffer");
         GSR_STAGE(GSR_STAGE_FINALIZE, launch_finalize(v.sorted_tile, cap, v.K_dev, v.ranges, stream), "finalize");
         // presort mode: the stable tile sort of rank-ordered instances is already canonical
-        if (!v.presort)
-            GSR_STAGE(GSR_STAGE_DEPTH_SORT, launch_tile_depth_sort(v.ranges, j.ty0 * j.gx, ntiles, cap, v.depth_key,
-                                                               v.sorted_gid, v.ovf, v.counters + kOvfCountSlot, v.ovf2,
-                                                               v.counters + kOvf2CountSlot, v.done, v.free_k,
-                                                               v.free_v, stream),
-                  "per-tile depth order");
+        if (!v.presort) GSR_STAGE(GSR_STAGE_DEPTH_SORT, depth_sort(false, nullptr), "per-tile depth order");
     }
+    F6Aux f6{};  // gsr_forward_aux (a full image: checked there)
     if (j.aux)
-        GSR_STAGE(GSR_STAGE_BLEND_FWD, launch_blend_forward_aux(*cam, j.rs->bg, v.ranges, v.sorted_gid, v.rec,
-                                                                v.depth_key, (j.rs->flags & GSR_FLAG_INVDEPTH) != 0,
-                                                                j.out_color, j.aux->depth, j.aux->alpha, v.final_T,
-                                                                v.accum, v.accum_z, v.term, v.ck, v.ckz, cap, stream,
-                                                                v.mk),
-                  "blend forward (aux)");
-    else
-        GSR_STAGE(GSR_STAGE_BLEND_FWD, launch_blend_forward(*cam, j.rs->bg, j.ty0, j.ty1, v.ranges, v.sorted_gid,
-                                                            v.rec, j.out_color, v.final_T, v.accum, v.term, v.ck, cap,
-                                                            stream, j.vgy, j.vh, v.mk),
-                  "blend forward");
+        f6 = {v.depth_key, j.aux->depth, j.aux->alpha, v.accum_z, v.ckz, (j.rs->flags & GSR_FLAG_INVDEPTH) ? 1 : 0};
+    GSR_STAGE(GSR_STAGE_BLEND_FWD, launch_blend_forward(*cam, j.rs->bg, j.ty0, j.ty1, v.ranges, v.sorted_gid, v.rec,
+                                                        j.out_color, v.final_T, v.accum, v.term, v.ck, cap, stream,
+                                                        j.vgy, j.vh, v.mk, j.aux ? &f6 : nullptr),
+              j.aux ? "blend forward (aux)" : "blend forward");
     return 0;
+}
+
+// The end of gsr_forward(_aux) and gsr_forward_views: phase 2 with the capacity the settings give, or
+// with exact sizing (max_rendered == 0) the host read of K first -- the sum of F1's count partials,
+// whose DMA phase 1's `pre` began.
+int fwd_sized_phase2(FwdJob& j, gsr_alloc_fn alloc_binning, void* ctx, hipStream_t stream, bool debug) {
+    long long cap = j.rs->max_rendered;
+    if (cap == 0) {
+        uint64_t ksum = 0;
+        if (j.n > 0) {
+            uint32_t cw[2 * kCountSlots];
+            const Views v = views(j.cam, j.n, j.bufs);
+            GSR_STAGE(GSR_STAGE_MISC, end_read(v.counters, cw, 2 * kCountSlots, stream), "read counts");
+            for (int i = 0; i < kCountSlots; ++i) ksum += cw[kCountSlots + i];
+        }
+        if (ksum > (uint64_t)INT32_MAX) return fail(-3, "num_rendered overflow (%llu)", (unsigned long long)ksum);
+        cap = (long long)ksum;
+        j.bufs->num_rendered = (int32_t)ksum;
+    }
+    return fwd_phase2(j, cap, alloc_binning, ctx, stream, debug);
 }
 
 // Per view of a batch: the sum of F1's 64 instance-count partials, as a u64 in two words.
@@ -497,19 +513,19 @@ __global__ __launch_bounds__(64) void batch_counts_kernel(CountPtrs p, uint32_t*
 }
 
 // F1 over Gaussians [0, P) with the count partials K is read from
-int run_preprocess(const gsr_camera* cam, const gsr_gaussians* gs, int ty0, int ty1, int32_t* radii, const Views& v,
-                   hipStream_t stream, bool debug) {
+int run_preprocess(const FwdJob& j, const gsr_gaussians* gs, int32_t* radii, const Views& v, hipStream_t stream,
+                   bool debug) {
     if (gs->P <= 0) return 0;
+    const gsr_camera* cam = j.cam;
     // SH clamp bits are stored by a full-image F1 only: a band's F1 evaluates the colour of its
     // own Gaussians alone, and B2 recomputes the bits (stored_flags)
-    const bool full = ty0 == 0 && ty1 == div_up(cam->height, kTile);
-    PreOut po{radii, v.depth_key, v.tiles, v.rec, v.rect, full ? v.flags : nullptr, v.counters};
+    PreOut po{radii, v.depth_key, v.tiles, v.rec, v.rect, full_image(cam, j.rs) ? v.flags : nullptr, v.counters};
     // the row-bucketed binning's pass-A row counts, from F1 itself (fwd_phase2 then skips them)
     if (use_rb_binning(gs->P, div_up(cam->width, kTile), div_up(cam->height, kTile))) {
         po.rb_hist = v.rb_histA;
         po.bsum = v.lookback + 16;  // the F2 scan's block partials (the lookback words are unused here)
     }
-    GSR_STAGE(GSR_STAGE_PREPROCESS, launch_preprocess(*cam, gauss_in(gs), ty0, ty1, po, stream), "preprocess");
+    GSR_STAGE(GSR_STAGE_PREPROCESS, launch_preprocess(*cam, gauss_in(gs), j.ty0, j.ty1, po, stream), "preprocess");
     return 0;
 }
 
@@ -526,41 +542,37 @@ int blend_backward(const gsr_camera* cam, const gsr_raster_settings* rs, const g
     if (int e = check_layout(cam, ty0, ty1, bufs)) return e;
     const Views v = views(cam, n, bufs);
     if (!alloc_scratch) return fail(-1, "null scratch allocator");
-    if (aux) {  // gsr_backward_aux (full image, aux buffers: checked by the caller)
-        float* partial = static_cast<float*>(alloc_scratch(ctx, PartLayout(cap, true).total));
-        if (!partial) return fail(-2, "allocation failed (scratch, %lld instances)", cap);
-        const bool inv = (bufs->layout & kBufInvDepth) != 0;
-        GSR_STAGE(GSR_STAGE_MISC, launch_clear_flags(partial, cap, stream), "clear partial flags");
-        GSR_STAGE(GSR_STAGE_BLEND_BWD, launch_blend_backward_aux(*cam, rs->bg, v.ranges, v.sorted_gid, v.rect, v.rec,
-                                                                 v.depth_key, inv, v.final_T, v.accum, v.accum_z,
-                                                                 dL_dpix, aux->dL_ddepth, aux->dL_dalpha, partial, cap,
-                                                                 v.term, v.ck, v.ckz, stream, v.mk),
-                  "blend backward (aux)");
-        GSR_STAGE(GSR_STAGE_GATHER, launch_gather_grad2d(v.offsets, partial, v.rec, cam->width, cam->height, cap,
-                                                         (int)n, v.presort ? v.rrect : nullptr, grad2d, stream, true),
-                  "gather grad2d (aux)");
-        return 0;
-    }
-    float* partial = static_cast<float*>(alloc_scratch(ctx, PartLayout(cap).total));
+    // aux: gsr_backward_aux (full image, aux buffers: checked by the caller)
+    const bool ax = aux != nullptr;
+    float* partial = static_cast<float*>(alloc_scratch(ctx, PartLayout(cap, ax).total));
     if (!partial) return fail(-2, "allocation failed (scratch, %lld instances)", cap);
+    const int inv = (bufs->layout & kBufInvDepth) ? 1 : 0;
+    B1Aux b1{};
+    if (ax) b1 = {v.depth_key, v.accum_z, aux->dL_ddepth, aux->dL_dalpha, v.ckz, nullptr, inv};
     // only the per-entry flag bytes are zeroed: the gather reads the entries B1 flagged
-    GSR_STAGE(GSR_STAGE_MISC, launch_clear_flags(partial, cap, stream), "clear partial flags");
+    GSR_STAGE(GSR_STAGE_MISC, launch_clear_flags(partial, cap, ax, stream), "clear partial flags");
     GSR_STAGE(GSR_STAGE_BLEND_BWD, launch_blend_backward(*cam, rs->bg, ty0, ty1, v.ranges, v.sorted_gid, v.rect, v.rec,
                                                          v.final_T, v.accum, dL_dpix, partial, cap, v.term, v.ck,
-                                                         stream, vgy, vh, v.mk),
-              "blend backward");
+                                                         stream, vgy, vh, v.mk, ax ? &b1 : nullptr),
+              ax ? "blend backward (aux)" : "blend backward");
     GSR_STAGE(GSR_STAGE_GATHER, launch_gather_grad2d(v.offsets, partial, v.rec, cam->width, vgy > 0 ? vh : cam->height,
-                                                     cap, (int)n,
-                                                     v.presort ? v.rrect : nullptr, grad2d, stream),
-              "gather grad2d");
+                                                     cap, (int)n, v.presort ? v.rrect : nullptr, grad2d, stream, ax),
+              ax ? "gather grad2d (aux)" : "gather grad2d");
     return 0;
+}
+
+// The per-entry 2D gradients (kPart floats each) the gather writes and B2 reads
+int alloc_grad2d(gsr_alloc_fn alloc_scratch, void* ctx, long long n, bool view_entries, float** grad2d) {
+    if (!alloc_scratch) return fail(-1, "null scratch allocator");
+    *grad2d = static_cast<float*>(alloc_scratch(ctx, sizeof(float) * kPart * (size_t)n));
+    if (*grad2d) return 0;
+    return view_entries ? fail(-2, "allocation failed (grad2d, %lld entries)", n)
+                        : fail(-2, "allocation failed (grad2d, P=%lld)", n);
 }
 
 // SH clamp bits for B2: stored by a full-image forward, else nullptr (B2 recomputes them)
 const uint32_t* stored_flags(const gsr_camera* cam, const gsr_raster_settings* rs, const uint32_t* flags) {
-    int ty0, ty1;
-    band(cam, rs, &ty0, &ty1);
-    return (ty0 == 0 && ty1 == div_up(cam->height, kTile)) ? flags : nullptr;
+    return full_image(cam, rs) ? flags : nullptr;
 }
 
 int check_grads(const gsr_gaussians* gs, const gsr_grads* g) {
@@ -612,15 +624,13 @@ int views_camera(int32_t V, const gsr_camera* cams, const gsr_gaussians* gs, con
                         cams[v].width, cams[v].height);
     }
     const int gy = div_up(cams[0].height, kTile);
-    if (rs->tile_y0 > 0 || rs->tile_y1 < gy) return fail(-1, "views: full-image views only");
+    if (!full_image(&cams[0], rs)) return fail(-1, "views: full-image views only");
     if ((long long)V * gy >= 65535) return fail(-1, "views: %d views of %d tile rows exceed the tile grid", V, gy);
     if ((long long)V * gs->P > INT32_MAX / 2) return fail(-1, "views: V * P too large");
     *tall = cams[0];
     tall->height = V * gy * kTile;
     return 0;
 }
-
-GaussIn shard_in(const gsr_gaussians* gs) { return gauss_in(gs); }
 
 }  // namespace
 
@@ -672,27 +682,14 @@ static int forward_one(const gsr_camera* cam, const gsr_gaussians* gs, const gsr
     j.n = gs->P;
     const bool exact = rs->max_rendered == 0;
     if (int e = fwd_phase1(j, alloc_geom, alloc_image, ctx, stream, debug, false, [&](const Views& v) {
-            if (int e2 = run_preprocess(cam, gs, j.ty0, j.ty1, radii, v, stream, debug)) return e2;
+            if (int e2 = run_preprocess(j, gs, radii, v, stream, debug)) return e2;
             j.rows_counted = true;
             // exact sizing: F1's count partials go to the host while the scan runs
             if (exact && gs->P > 0) GSR_CHECK_HIP(begin_read(v.counters, 2 * kCountSlots, stream), "read counts");
             return 0;
         }))
         return e;
-    long long cap = rs->max_rendered;
-    if (exact) {
-        uint64_t ksum = 0;
-        if (gs->P > 0) {
-            uint32_t cw[2 * kCountSlots];
-            const Views v = views(cam, j.n, bufs);
-            GSR_STAGE(GSR_STAGE_MISC, end_read(v.counters, cw, 2 * kCountSlots, stream), "read counts");
-            for (int i = 0; i < kCountSlots; ++i) ksum += cw[kCountSlots + i];
-        }
-        if (ksum > (uint64_t)INT32_MAX) return fail(-3, "num_rendered overflow (%llu)", (unsigned long long)ksum);
-        cap = (long long)ksum;
-        bufs->num_rendered = (int32_t)ksum;
-    }
-    return fwd_phase2(j, cap, alloc_binning, ctx, stream, debug);
+    return fwd_sized_phase2(j, alloc_binning, ctx, stream, debug);
 }
 
 int gsr_forward(const gsr_camera* cam, const gsr_gaussians* gs, const gsr_raster_settings* rs,
@@ -710,7 +707,7 @@ int gsr_forward_aux(const gsr_camera* cam, const gsr_gaussians* gs, const gsr_ra
     g_err.clear();
     if (int e = validate(cam, gs, rs)) return e;
     if (!aux || !aux->depth || !aux->alpha) return fail(-1, "aux: null gsr_aux_out / depth / alpha output");
-    if (rs->tile_y0 > 0 || rs->tile_y1 < div_up(cam->height, kTile))
+    if (!full_image(cam, rs))
         return fail(-1, "aux: full images only (tile rows [%d, %d) of %d are a band)", rs->tile_y0, rs->tile_y1,
                     div_up(cam->height, kTile));
     return forward_one(cam, gs, rs, out_color, radii, alloc_geom, alloc_binning, alloc_image, ctx, bufs, stream_, aux);
@@ -753,15 +750,14 @@ int gsr_forward_batch(int32_t V, const gsr_camera* cams, const gsr_gaussians* gs
     jobs.reserve(V);
     for (int v = 0; v < V; ++v) {
         if (int e = validate(&cams[v], gs, rs)) return e;
-        if (rs->tile_y0 > 0 || rs->tile_y1 < div_up(cams[v].height, kTile))
-            return fail(-1, "batch: full-image views only (view %d)", v);
+        if (!full_image(&cams[v], rs)) return fail(-1, "batch: full-image views only (view %d)", v);
         if (!out_colors[v] || (gs->P > 0 && !radii[v])) return fail(-1, "batch: null output of view %d", v);
         jobs.push_back(FwdJob{&cams[v], rs, out_colors[v], &bufs[v]});
         jobs[v].n = gs->P;
         int32_t* rad = gs->P > 0 ? radii[v] : nullptr;
         if (int e = fwd_phase1(jobs[v], alloc_geom, alloc_image, ctx, stream, debug, false, [&](const Views& vw) {
                 jobs[v].rows_counted = true;
-                return run_preprocess(&cams[v], gs, jobs[v].ty0, jobs[v].ty1, rad, vw, stream, debug);
+                return run_preprocess(jobs[v], gs, rad, vw, stream, debug);
             }))
             return e;
     }
@@ -819,20 +815,7 @@ int gsr_forward_views(int32_t V, const gsr_camera* cams, const gsr_gaussians* gs
             return 0;
         }))
         return e;
-    long long cap = rs->max_rendered;
-    if (exact) {
-        uint64_t ksum = 0;
-        if (gs->P > 0) {
-            uint32_t cw[2 * kCountSlots];
-            const Views v = views(&tall, j.n, bufs);
-            GSR_STAGE(GSR_STAGE_MISC, end_read(v.counters, cw, 2 * kCountSlots, stream), "read counts");
-            for (int i = 0; i < kCountSlots; ++i) ksum += cw[kCountSlots + i];
-        }
-        if (ksum > (uint64_t)INT32_MAX) return fail(-3, "num_rendered overflow (%llu)", (unsigned long long)ksum);
-        cap = (long long)ksum;
-        bufs->num_rendered = (int32_t)ksum;
-    }
-    return fwd_phase2(j, cap, alloc_binning, ctx, stream, debug);
+    return fwd_sized_phase2(j, alloc_binning, ctx, stream, debug);
 }
 
 int gsr_backward_views(int32_t V, const gsr_camera* cams, const gsr_gaussians* gs, const gsr_raster_settings* rs,
@@ -847,14 +830,13 @@ int gsr_backward_views(int32_t V, const gsr_camera* cams, const gsr_gaussians* g
     const long long n = (long long)V * gs->P;
     if (!bufs || bufs->n_local != n) return fail(-1, "forward buffers do not match V * P view entries");
     if (int e = check_layout(&tall, 0, div_up(tall.height, kTile), bufs)) return e;
-    if (!alloc_scratch) return fail(-1, "null scratch allocator");
     hipStream_t stream = (hipStream_t)stream_;
     const bool debug = (rs->flags & GSR_FLAG_DEBUG) != 0;
     gsr_raster_settings rv = *rs;
     rv.tile_y0 = 0;
     rv.tile_y1 = INT32_MAX;
-    float* grad2d = static_cast<float*>(alloc_scratch(ctx, sizeof(float) * kPart * (size_t)n));
-    if (!grad2d) return fail(-2, "allocation failed (grad2d, %lld entries)", n);
+    float* grad2d;
+    if (int e = alloc_grad2d(alloc_scratch, ctx, n, true, &grad2d)) return e;
     if (int e = blend_backward(&tall, &rv, bufs, dL_dpix, alloc_scratch, ctx, grad2d, stream, debug,
                                div_up(cams[0].height, kTile), cams[0].height))
         return e;
@@ -887,11 +869,10 @@ int gsr_backward_views(int32_t V, const gsr_camera* cams, const gsr_gaussians* g
     return 0;
 }
 
-int gsr_backward(const gsr_camera* cam, const gsr_gaussians* gs, const gsr_raster_settings* rs,
-                 const gsr_buffers* bufs, const float* dL_dpix, gsr_alloc_fn alloc_scratch, void* ctx,
-                 const gsr_grads* grads, void* stream_) {
-    g_err.clear();
-    if (int e = validate(cam, gs, rs)) return e;
+// gsr_backward / gsr_backward_aux (aux != nullptr, on a full image: checked by the caller), after validate()
+static int backward_one(const gsr_camera* cam, const gsr_gaussians* gs, const gsr_raster_settings* rs,
+                        const gsr_buffers* bufs, const float* dL_dpix, gsr_alloc_fn alloc_scratch, void* ctx,
+                        const gsr_grads* grads, void* stream_, const gsr_aux_grads* aux) {
     if (gs->P == 0) return 0;
     if (int e = check_grads(gs, grads)) return e;
     if (!bufs || bufs->n_local != gs->P) return fail(-1, "forward buffers do not match the Gaussians");
@@ -900,18 +881,34 @@ int gsr_backward(const gsr_camera* cam, const gsr_gaussians* gs, const gsr_raste
         band(cam, rs, &ty0, &ty1);
         if (int e = check_layout(cam, ty0, ty1, bufs)) return e;  // before any allocation
     }
+    const bool inv = (rs->flags & GSR_FLAG_INVDEPTH) != 0;
+    if (aux && !(bufs->layout & kBufAux))
+        return fail(GSR_ERR_LAYOUT, "gsr_backward_aux: gsr_buffers.layout = 0x%08x is not gsr_forward_aux's "
+                                    "(no GSR_LAYOUT_AUX): the buffers hold no depth sums",
+                    bufs->layout);
+    if (aux && inv != ((bufs->layout & kBufInvDepth) != 0))
+        return fail(GSR_ERR_LAYOUT, "gsr_backward_aux: GSR_FLAG_INVDEPTH is %s but the forward ran %s it",
+                    inv ? "set" : "clear", inv ? "without" : "with");
     hipStream_t stream = (hipStream_t)stream_;
     const bool debug = (rs->flags & GSR_FLAG_DEBUG) != 0;
-    if (!alloc_scratch) return fail(-1, "null scratch allocator");
-    float* grad2d = static_cast<float*>(alloc_scratch(ctx, sizeof(float) * kPart * (size_t)gs->P));
-    if (!grad2d) return fail(-2, "allocation failed (grad2d, P=%d)", gs->P);
-    if (int e = blend_backward(cam, rs, bufs, dL_dpix, alloc_scratch, ctx, grad2d, stream, debug)) return e;
+    float* grad2d;
+    if (int e = alloc_grad2d(alloc_scratch, ctx, gs->P, false, &grad2d)) return e;
+    if (int e = blend_backward(cam, rs, bufs, dL_dpix, alloc_scratch, ctx, grad2d, stream, debug, 0, 0, aux)) return e;
     const Views v = views(cam, gs->P, bufs);
+    // a full image's stored SH clamp bits; aux: grad2d slot 9 is dL/dz (1) or dL/d(1/z) (2)
     GSR_STAGE(GSR_STAGE_PREPROCESS_BWD, launch_preprocess_backward(*cam, gauss_in(gs), 0, gs->P, v.depth_key,
                                                                    stored_flags(cam, rs, v.flags), grad2d,
-                                                                   grad_out(grads), stream),
-              "preprocess backward");
+                                                                   grad_out(grads), stream, aux ? (inv ? 2 : 1) : 0),
+              aux ? "preprocess backward (aux)" : "preprocess backward");
     return 0;
+}
+
+int gsr_backward(const gsr_camera* cam, const gsr_gaussians* gs, const gsr_raster_settings* rs,
+                 const gsr_buffers* bufs, const float* dL_dpix, gsr_alloc_fn alloc_scratch, void* ctx,
+                 const gsr_grads* grads, void* stream_) {
+    g_err.clear();
+    if (int e = validate(cam, gs, rs)) return e;
+    return backward_one(cam, gs, rs, bufs, dL_dpix, alloc_scratch, ctx, grads, stream_, nullptr);
 }
 
 int gsr_backward_aux(const gsr_camera* cam, const gsr_gaussians* gs, const gsr_raster_settings* rs,
@@ -920,32 +917,10 @@ int gsr_backward_aux(const gsr_camera* cam, const gsr_gaussians* gs, const gsr_r
     g_err.clear();
     if (int e = validate(cam, gs, rs)) return e;
     if (!aux) return fail(-1, "aux: null gsr_aux_grads");
-    const int gy = div_up(cam->height, kTile);
-    if (rs->tile_y0 > 0 || rs->tile_y1 < gy)
-        return fail(-1, "aux: full images only (tile rows [%d, %d) of %d are a band)", rs->tile_y0, rs->tile_y1, gy);
-    if (gs->P == 0) return 0;
-    if (int e = check_grads(gs, grads)) return e;
-    if (!bufs || bufs->n_local != gs->P) return fail(-1, "forward buffers do not match the Gaussians");
-    if (int e = check_layout(cam, 0, gy, bufs)) return e;  // before any allocation
-    if (!(bufs->layout & kBufAux))
-        return fail(GSR_ERR_LAYOUT, "gsr_backward_aux: gsr_buffers.layout = 0x%08x is not gsr_forward_aux's "
-                                    "(no GSR_LAYOUT_AUX): the buffers hold no depth sums",
-                    bufs->layout);
-    const bool inv = (rs->flags & GSR_FLAG_INVDEPTH) != 0;
-    if (inv != ((bufs->layout & kBufInvDepth) != 0))
-        return fail(GSR_ERR_LAYOUT, "gsr_backward_aux: GSR_FLAG_INVDEPTH is %s but the forward ran %s it",
-                    inv ? "set" : "clear", inv ? "without" : "with");
-    hipStream_t stream = (hipStream_t)stream_;
-    const bool debug = (rs->flags & GSR_FLAG_DEBUG) != 0;
-    if (!alloc_scratch) return fail(-1, "null scratch allocator");
-    float* grad2d = static_cast<float*>(alloc_scratch(ctx, sizeof(float) * kPart * (size_t)gs->P));
-    if (!grad2d) return fail(-2, "allocation failed (grad2d, P=%d)", gs->P);
-    if (int e = blend_backward(cam, rs, bufs, dL_dpix, alloc_scratch, ctx, grad2d, stream, debug, 0, 0, aux)) return e;
-    const Views v = views(cam, gs->P, bufs);
-    GSR_STAGE(GSR_STAGE_PREPROCESS_BWD, launch_preprocess_backward(*cam, gauss_in(gs), 0, gs->P, v.depth_key, v.flags,
-                                                                   grad2d, grad_out(grads), stream, inv ? 2 : 1),
-              "preprocess backward (aux)");
-    return 0;
+    if (!full_image(cam, rs))
+        return fail(-1, "aux: full images only (tile rows [%d, %d) of %d are a band)", rs->tile_y0, rs->tile_y1,
+                    div_up(cam->height, kTile));
+    return backward_one(cam, gs, rs, bufs, dL_dpix, alloc_scratch, ctx, grads, stream_, aux);
 }
 
 int gsr_backward_blend(const gsr_camera* cam, const gsr_gaussians* gs, const gsr_raster_settings* rs,
@@ -999,7 +974,7 @@ int gsr_shard_forward(const gsr_camera* cam, const gsr_gaussians* gs, const gsr_
     uint4* rect = at<uint4>(shard_state, gl.rect);
     if (P > 0) {
         PreOut po{radii, depth_key, tiles, rec, rect, at<uint32_t>(shard_state, gl.flags), nullptr};
-        GSR_STAGE(GSR_STAGE_PREPROCESS, launch_preprocess(*cam, shard_in(gs), 0, gy, po, stream), "preprocess");
+        GSR_STAGE(GSR_STAGE_PREPROCESS, launch_preprocess(*cam, gauss_in(gs), 0, gy, po, stream), "preprocess");
     }
     GSR_STAGE(GSR_STAGE_EXCHANGE, launch_pack_splats(tiles, rect, depth_key, rec, P, br,
                                                      at<uint32_t>(shard_state, sl.partials), static_cast<char*>(send),
@@ -1069,7 +1044,7 @@ int gsr_shard_backward(const gsr_camera* cam, const gsr_gaussians* gs, const gsr
     const uint4* rect = at<uint4>(shard_state, gl.rect);
     // B2 sums the bands' returned rows itself (no grad2d round trip, one launch fewer)
     BandSum bs{tiles, rect, at<uint32_t>(shard_state, sl.slot_of), static_cast<const float4*>(grad_recv), pair_cap, br};
-    GSR_STAGE(GSR_STAGE_PREPROCESS_BWD, launch_preprocess_backward_banded(*cam, shard_in(gs),
+    GSR_STAGE(GSR_STAGE_PREPROCESS_BWD, launch_preprocess_backward_banded(*cam, gauss_in(gs),
                                                                           at<uint32_t>(shard_state, gl.depth_key),
                                                                           at<uint32_t>(shard_state, gl.flags), bs,
                                                                           grad_out(grads), stream),

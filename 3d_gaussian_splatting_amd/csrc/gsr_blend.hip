@@ -173,23 +173,6 @@ constexpr int kF6Wpe = 8;
 // LDS, instructions -- is the plain one.  v_i, the value the channel blends, is the Gaussian's
 // view-space depth (the float whose bits are its depth key) or its reciprocal; it is staged in LDS
 // beside the record at batch load (the 48-byte record has no free lane).
-struct F6Aux {
-    const uint32_t* depth_key;  // per Gaussian: bits of the f32 view-space depth
-    float* out_depth;           // H x W: sum w v
-    float* out_alpha;           // H x W: sum w (= 1 - final T)
-    float* accum_z;             // H x W: the depth sum, for B1
-    float* ckz;                 // per checkpoint slot 256 floats: the depth sum so far
-    int inv;                    // v = 1 / z
-};
-struct B1Aux {
-    const uint32_t* depth_key;
-    const float* accum_z;
-    const float* dL_ddepth;  // H x W or nullptr (zero)
-    const float* dL_dalpha;  // H x W or nullptr (zero)
-    const float* ckz;
-    float* pz;               // per partial entry: the tenth moment, sum w dL/ddepth
-    int inv;
-};
 template <class T>
 __device__ __forceinline__ T aux_arg() { return T{}; }
 template <class T>
@@ -931,21 +914,37 @@ static BlendGeom make_geo(const gsr_camera& cam, const float bg[3], int ty0, int
     return g;
 }
 
+// The tile count a pass picks its instantiation by (and with it the B1 chunk work): the tiles of
+// ONE image, so views mode chunks every tile as a per-view call does, which keeps its gradients
+// bit-identical.  The aux channel has no say in it (same batches, same chunk quota): a forward's
+// chunk table -- and with it every colour gradient bit -- does not depend on whether it rides along.
+static long long image_tiles(const BlendGeom& geo, int vgy) {
+    return vgy > 0 ? (long long)geo.vgy * geo.grid_x : geo.nwg;
+}
+// the aux channel comes with full images only, outside views mode
+static bool aux_ok(const void* aux, const gsr_camera& cam, int ty0, int ty1, int vgy) {
+    return !aux || (vgy <= 0 && ty0 == 0 && ty1 == div_up(cam.height, kTile));
+}
+
 int launch_blend_forward(const gsr_camera& cam, const float bg[3], int ty0, int ty1,
                          const uint2* ranges, const uint32_t* sorted_gid, const float4* rec,
                          float* out_color, float* final_T, float* accum, uint32_t* term, float4* ck, long long cap,
-                         hipStream_t s, int vgy, int vh, uint8_t* mk) {
+                         hipStream_t s, int vgy, int vh, uint8_t* mk, const F6Aux* aux) {
+    if (!aux_ok(aux, cam, ty0, ty1, vgy)) return (int)hipErrorInvalidValue;
     const BlendGeom geo = make_geo(cam, bg, ty0, ty1, cap, vgy, vh);
     if (geo.nwg <= 0) return 0;
-    // the variant (and with it the B1 chunk work) follows the tiles of ONE image: views mode then
-    // chunks every tile as a per-view call does, which keeps its gradients bit-identical
-    const long long sel = vgy > 0 ? (long long)geo.vgy * geo.grid_x : geo.nwg;
-    if (sel >= kF6BandTiles)
-        hipLaunchKernelGGL(blend_forward_kernel<kF6FullWaves>, dim3(geo.nwg), dim3(64 * kF6FullWaves), 0, s, geo,
-                           ranges, sorted_gid, rec, out_color, final_T, accum, term, ck, mk);
-    else
-        hipLaunchKernelGGL(blend_forward_kernel<kF6BandWaves>, dim3(geo.nwg), dim3(64 * kF6BandWaves), 0, s, geo,
-                           ranges, sorted_gid, rec, out_color, final_T, accum, term, ck, mk);
+    auto launch = [&](auto nw, auto... ax) {
+        constexpr int NW = decltype(nw)::value;
+        hipLaunchKernelGGL((blend_forward_kernel<NW, decltype(ax)...>), dim3(geo.nwg), dim3(64 * NW), 0, s, geo, ranges,
+                           sorted_gid, rec, out_color, final_T, accum, term, ck, mk, ax...);
+    };
+    auto pick = [&](auto... ax) {
+        if (image_tiles(geo, vgy) >= kF6BandTiles)
+            launch(std::integral_constant<int, kF6FullWaves>{}, ax...);
+        else
+            launch(std::integral_constant<int, kF6BandWaves>{}, ax...);
+    };
+    aux ? pick(*aux) : pick();
     return (int)hipGetLastError();
 }
 
@@ -959,73 +958,33 @@ int launch_blend_backward(const gsr_camera& cam, const float bg[3], int ty0, int
                           const float4* rec, const float* final_T,
                           const float* accum, const float* dL_dpix, float* partial, long long cap,
                           const uint32_t* term, const float4* ck, hipStream_t s, int vgy, int vh,
-                          const uint8_t* mk) {
+                          const uint8_t* mk, const B1Aux* aux) {
+    if (!aux_ok(aux, cam, ty0, ty1, vgy)) return (int)hipErrorInvalidValue;
     const BlendGeom geo = make_geo(cam, bg, ty0, ty1, cap, vgy, vh);
     if (geo.nwg <= 0) return 0;
-    const PartLayout pl(cap);
-    char* base = reinterpret_cast<char*>(partial);
+    const PartLayout pl(cap, aux != nullptr);
     const int blocks = 8 * (geo.nwg / 8 + 1) * kMaxChunks;
-    auto* p8 = reinterpret_cast<float*>(base + pl.p8);
-    auto* p1 = reinterpret_cast<float*>(base + pl.p1);
-    auto* fl = reinterpret_cast<uint8_t*>(base + pl.fl);
-    const long long sel = vgy > 0 ? (long long)geo.vgy * geo.grid_x : geo.nwg;  // one image's tiles
-    if (sel < kF6BandTiles)
-        hipLaunchKernelGGL(blend_backward_kernel<true>, dim3(blocks), dim3(64), 0, s, geo, ranges, sorted_gid,
-                           rect, rec, final_T, accum, dL_dpix, p8, p1, fl, term, ck, mk);
-    else
-        hipLaunchKernelGGL(blend_backward_kernel<false>, dim3(blocks), dim3(64), 0, s, geo, ranges, sorted_gid, rect, rec,
-                           final_T, accum, dL_dpix, p8, p1, fl, term, ck, mk);
+    auto launch = [&](auto pf, auto... ax) {
+        hipLaunchKernelGGL((blend_backward_kernel<decltype(pf)::value, decltype(ax)...>), dim3(blocks), dim3(64), 0, s,
+                           geo, ranges, sorted_gid, rect, rec, final_T, accum, dL_dpix, at<float>(partial, pl.p8),
+                           at<float>(partial, pl.p1), at<uint8_t>(partial, pl.fl), term, ck, mk, ax...);
+    };
+    auto pick = [&](auto... ax) {
+        if (image_tiles(geo, vgy) < kF6BandTiles)
+            launch(std::true_type{}, ax...);  // prefetching B1
+        else
+            launch(std::false_type{}, ax...);
+    };
+    B1Aux ax = aux ? *aux : B1Aux{};
+    ax.pz = at<float>(partial, pl.pz);
+    aux ? pick(ax) : pick();
     return (int)hipGetLastError();
 }
 
-// The aux launches choose their instantiations by the image's tile count exactly as the plain ones
-// do (same batches, same chunk quota), so a forward's chunk table -- and with it every colour
-// gradient bit -- does not depend on whether the aux channel rides along.
-int launch_blend_forward_aux(const gsr_camera& cam, const float bg[3], const uint2* ranges,
-                             const uint32_t* sorted_gid, const float4* rec, const uint32_t* depth_key, bool inv,
-                             float* out_color, float* out_depth, float* out_alpha, float* final_T, float* accum,
-                             float* accum_z, uint32_t* term, float4* ck, float* ckz, long long cap, hipStream_t s,
-                             uint8_t* mk) {
-    const BlendGeom geo = make_geo(cam, bg, 0, div_up(cam.height, kTile), cap, 0, 0);
-    if (geo.nwg <= 0) return 0;
-    const F6Aux ax{depth_key, out_depth, out_alpha, accum_z, ckz, inv ? 1 : 0};
-    if (geo.nwg >= kF6BandTiles)
-        hipLaunchKernelGGL((blend_forward_kernel<kF6FullWaves, F6Aux>), dim3(geo.nwg), dim3(64 * kF6FullWaves), 0, s,
-                           geo, ranges, sorted_gid, rec, out_color, final_T, accum, term, ck, mk, ax);
-    else
-        hipLaunchKernelGGL((blend_forward_kernel<kF6BandWaves, F6Aux>), dim3(geo.nwg), dim3(64 * kF6BandWaves), 0, s,
-                           geo, ranges, sorted_gid, rec, out_color, final_T, accum, term, ck, mk, ax);
-    return (int)hipGetLastError();
-}
-
-int launch_blend_backward_aux(const gsr_camera& cam, const float bg[3], const uint2* ranges,
-                              const uint32_t* sorted_gid, const uint4* rect, const float4* rec,
-                              const uint32_t* depth_key, bool inv, const float* final_T, const float* accum,
-                              const float* accum_z, const float* dL_dpix, const float* dL_ddepth,
-                              const float* dL_dalpha, float* partial, long long cap, const uint32_t* term,
-                              const float4* ck, const float* ckz, hipStream_t s, const uint8_t* mk) {
-    const BlendGeom geo = make_geo(cam, bg, 0, div_up(cam.height, kTile), cap, 0, 0);
-    if (geo.nwg <= 0) return 0;
-    const PartLayout pl(cap, true);
-    char* base = reinterpret_cast<char*>(partial);
-    const int blocks = 8 * (geo.nwg / 8 + 1) * kMaxChunks;
-    auto* p8 = reinterpret_cast<float*>(base + pl.p8);
-    auto* p1 = reinterpret_cast<float*>(base + pl.p1);
-    auto* fl = reinterpret_cast<uint8_t*>(base + pl.fl);
-    const B1Aux ax{depth_key, accum_z, dL_ddepth, dL_dalpha, ckz, reinterpret_cast<float*>(base + pl.pz), inv ? 1 : 0};
-    if (geo.nwg < kF6BandTiles)
-        hipLaunchKernelGGL((blend_backward_kernel<true, B1Aux>), dim3(blocks), dim3(64), 0, s, geo, ranges,
-                           sorted_gid, rect, rec, final_T, accum, dL_dpix, p8, p1, fl, term, ck, mk, ax);
-    else
-        hipLaunchKernelGGL((blend_backward_kernel<false, B1Aux>), dim3(blocks), dim3(64), 0, s, geo, ranges,
-                           sorted_gid, rect, rec, final_T, accum, dL_dpix, p8, p1, fl, term, ck, mk, ax);
-    return (int)hipGetLastError();
-}
-
-int launch_clear_flags(float* partial, long long cap, hipStream_t s) {
+int launch_clear_flags(float* partial, long long cap, bool aux, hipStream_t s) {
     if (cap <= 0) return 0;
-    const PartLayout pl(cap);
-    return (int)hipMemsetAsync(reinterpret_cast<char*>(partial) + pl.fl, 0, (size_t)cap, s);
+    return (int)hipMemsetAsync(at<uint8_t>(partial, PartLayout(cap, aux).fl), 0, (size_t)cap, s);
 }
 
 }  // namespace gsr
+

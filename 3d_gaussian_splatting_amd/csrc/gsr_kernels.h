@@ -125,45 +125,43 @@ int launch_tile_depth_sort(const uint2* ranges, int tile0, int ntiles, long long
 // the register forms need nothing else; tile_depth_sort_big then also puts runs of equal depth keys
 // into gid order.
 
+// The depth / alpha channel of F6 and B1 (gsr_forward_aux, gsr_backward_aux; full images outside views
+// mode only), as the launchers take it and the kernels get it.  v = depth_key[g] as a float, or 1 / that.
+struct F6Aux {
+    const uint32_t* depth_key;     // per Gaussian: bits of the f32 view-space depth
+    float *out_depth, *out_alpha;  // H x W: sum w v and sum w (= 1 - final T)
+    float *accum_z, *ckz;  // the depth sum for B1: H x W, and so far per checkpoint slot (256 floats each)
+    int inv;               // v = 1 / z
+};
+struct B1Aux {
+    const uint32_t* depth_key;
+    const float *accum_z, *dL_ddepth, *dL_dalpha, *ckz;  // the gradients: H x W or nullptr (zero)
+    float* pz;  // per partial entry: the tenth moment, sum w dL/ddepth (the launcher sets it: PartLayout.pz)
+    int inv;
+};
+
 // F6: per-tile front-to-back blend -> colour, final T, colour sum without background, the
 // tile's termination index term[], the B1 chunk checkpoints (ck: the binning buffer's
-// ck_pool_slots(cap, tiles of the image) slots, chunk slot ck_slot_of(...), gsr_internal.h)
+// ck_pool_slots(cap, tiles of the image) slots, chunk slot ck_slot_of(...), gsr_internal.h).
+// aux adds its outputs; the colour, the chunk table and every other output stay bit for bit.
 int launch_blend_forward(const gsr_camera& cam, const float bg[3], int ty0, int ty1,
                          const uint2* ranges, const uint32_t* sorted_gid, const float4* rec,
                          float* out_color, float* final_T, float* accum, uint32_t* term, float4* ck, long long cap,
-                         hipStream_t s, int vgy = 0, int vh = 0, uint8_t* mk = nullptr);
-
-// F6 with the depth and alpha channels (gsr_forward_aux; full images only): besides the above,
-// out_depth = sum w v and out_alpha = sum w per pixel (v = depth_key[g] as a float, or its
-// reciprocal when inv), the depth sum into accum_z and into every checkpoint's ckz words.  The
-// colour, the chunk table and every other output are the plain launch's, bit for bit.
-int launch_blend_forward_aux(const gsr_camera& cam, const float bg[3], const uint2* ranges,
-                             const uint32_t* sorted_gid, const float4* rec, const uint32_t* depth_key, bool inv,
-                             float* out_color, float* out_depth, float* out_alpha, float* final_T, float* accum,
-                             float* accum_z, uint32_t* term, float4* ck, float* ckz, long long cap, hipStream_t s,
-                             uint8_t* mk);
-// B1 with the depth / alpha gradients (dL_ddepth, dL_dalpha: H x W, nullable = zero): the tenth
-// moment sum w dL/ddepth goes to PartLayout(cap, true).pz; partial: PartLayout(cap, true).
-int launch_blend_backward_aux(const gsr_camera& cam, const float bg[3], const uint2* ranges,
-                              const uint32_t* sorted_gid, const uint4* rect, const float4* rec,
-                              const uint32_t* depth_key, bool inv, const float* final_T, const float* accum,
-                              const float* accum_z, const float* dL_dpix, const float* dL_ddepth,
-                              const float* dL_dalpha, float* partial, long long cap, const uint32_t* term,
-                              const float4* ck, const float* ckz, hipStream_t s, const uint8_t* mk);
+                         hipStream_t s, int vgy = 0, int vh = 0, uint8_t* mk = nullptr, const F6Aux* aux = nullptr);
 
 // F6 writes term[t] (see kMaxChunks) and the B1 chunk checkpoints `ck` (ImgLayout.ck).
-// B1: per-tile front-to-back gradients -> per-instance partial entry j (PartLayout(cap)), where
+// B1: per-tile front-to-back gradients -> per-instance partial entry j (PartLayout(cap, aux)), where
 // the emission index j = inst_start[g] + row-major index of the tile in g's band-clipped rect.
 // B1 writes the entries of the records that changed a pixel and sets their flag byte
 // (PartLayout.fl); launch_clear_flags zeroes the flags (K bytes) and must precede it.  The
 // gather reads only flagged entries, so the 36-B entries are never cleared.
-int launch_clear_flags(float* partial, long long cap, hipStream_t s);
+int launch_clear_flags(float* partial, long long cap, bool aux, hipStream_t s);
 int launch_blend_backward(const gsr_camera& cam, const float bg[3], int ty0, int ty1,
                           const uint2* ranges, const uint32_t* sorted_gid, const uint4* rect,
                           const float4* rec, const float* final_T,
                           const float* accum, const float* dL_dpix, float* partial, long long cap,
                           const uint32_t* term, const float4* ck, hipStream_t s, int vgy = 0, int vh = 0,
-                          const uint8_t* mk = nullptr);
+                          const uint8_t* mk = nullptr, const B1Aux* aux = nullptr);
 // (vgy, vh: views mode -- bands of vgy tile rows per view, vh valid pixel rows each; 0 = one image)
 
 // record layout constants shared by preprocess and the blend kernels

@@ -58,34 +58,36 @@ const float* fptr(const torch::Tensor& t, const char* name, int64_t P, int64_t p
     return t.data_ptr<float>();
 }
 
-gsr_gaussians make_gaussians(const RasterSettings& rs, const torch::Tensor& means3D,
-                             const torch::Tensor& sh_dc, const torch::Tensor& sh_rest,
-                             const torch::Tensor& colors, const torch::Tensor& opac,
-                             const torch::Tensor& scales, const torch::Tensor& rots,
-                             const torch::Tensor& cov3D) {
+// the tensor arguments of a rasterization, in the order of the autograd Functions' forward()
+// (means2D only receives a gradient)
+struct Inputs {
+    torch::Tensor means3D, means2D, sh_dc, sh_rest, colors, opac, scales, rots, cov3D;
+};
+
+gsr_gaussians make_gaussians(const RasterSettings& rs, const Inputs& in) {
     gsr_gaussians g{};
-    const int64_t P = means3D.size(0);
+    const int64_t P = in.means3D.size(0);
     g.P = (int32_t)P;
     g.sh_degree = rs.sh_degree;
     g.scale_modifier = rs.scale_modifier;
-    g.means3D = fptr(means3D, "means3D", P, 3);
-    g.opacities = fptr(opac, "opacities", P, 1);
-    if (present(colors)) {
-        g.colors_precomp = fptr(colors, "colors_precomp", P, 3);
+    g.means3D = fptr(in.means3D, "means3D", P, 3);
+    g.opacities = fptr(in.opac, "opacities", P, 1);
+    if (present(in.colors)) {
+        g.colors_precomp = fptr(in.colors, "colors_precomp", P, 3);
         g.sh_degree = 0;
     } else {
-        g.sh_dc = fptr(sh_dc, "sh_dc", P, 3);
-        if (present(sh_rest)) {
-            const int64_t M = sh_rest.numel() / std::max<int64_t>(P, 1) / 3;
-            g.sh_rest = fptr(sh_rest, "sh_rest", P, 3 * M);
+        g.sh_dc = fptr(in.sh_dc, "sh_dc", P, 3);
+        if (present(in.sh_rest)) {
+            const int64_t M = in.sh_rest.numel() / std::max<int64_t>(P, 1) / 3;
+            g.sh_rest = fptr(in.sh_rest, "sh_rest", P, 3 * M);
             g.sh_rest_coeffs = (int32_t)M;
         }
     }
-    if (present(cov3D)) {
-        g.cov3D_precomp = fptr(cov3D, "cov3D_precomp", P, 6);
+    if (present(in.cov3D)) {
+        g.cov3D_precomp = fptr(in.cov3D, "cov3D_precomp", P, 6);
     } else {
-        g.scales = fptr(scales, "scales", P, 3);
-        g.rotations = fptr(rots, "rotations", P, 4);
+        g.scales = fptr(in.scales, "scales", P, 3);
+        g.rotations = fptr(in.rots, "rotations", P, 4);
     }
     return g;
 }
@@ -104,11 +106,9 @@ void* cur_stream() { return detail::current_stream(); }
 
 using FwdResult = detail::Frame;
 
-FwdResult forward_impl(const RasterCamera& cam, const RasterSettings& rs, const torch::Tensor& means3D,
-                       const torch::Tensor& sh_dc, const torch::Tensor& sh_rest,
-                       const torch::Tensor& colors, const torch::Tensor& opac,
-                       const torch::Tensor& scales, const torch::Tensor& rots,
-                       const torch::Tensor& cov3D, bool aux = false, bool inverse_depth = false) {
+FwdResult forward_impl(const RasterCamera& cam, const RasterSettings& rs, const Inputs& in, bool aux = false,
+                       bool inverse_depth = false) {
+    const torch::Tensor& means3D = in.means3D;
     TORCH_CHECK(means3D.dim() == 2 && means3D.size(1) == 3, "means3D must be (P,3)");
     const int64_t P = means3D.size(0);
     auto dev = means3D.device();
@@ -117,7 +117,7 @@ FwdResult forward_impl(const RasterCamera& cam, const RasterSettings& rs, const 
     r.color = torch::empty({3, cam.height, cam.width}, fopt);
     r.radii = torch::empty({P}, fopt.dtype(torch::kInt32));
     const gsr_camera c = cam.to_c();
-    const gsr_gaussians g = make_gaussians(rs, means3D, sh_dc, sh_rest, colors, opac, scales, rots, cov3D);
+    const gsr_gaussians g = make_gaussians(rs, in);
     gsr_raster_settings s = make_settings(rs);
     AllocCtx geom{dev, {}}, bin{dev, {}}, img{dev, {}};
     gsr_buffers b{};
@@ -163,62 +163,48 @@ gsr_buffers buffers_of(const torch::Tensor& geom, const torch::Tensor& binning, 
 using torch::autograd::AutogradContext;
 using torch::autograd::variable_list;
 
-// What both autograd Functions keep from forward to backward, and how backward gets it back.
-void save_frame(AutogradContext* ctx, const RasterCamera& cam, const RasterSettings& rs, const FwdResult& r,
-                const torch::Tensor& means2D) {
-    ctx->saved_data["has_m2d"] = present(means2D);
-    ctx->saved_data["K"] = (int64_t)r.bufs.num_rendered;
-    ctx->saved_data["cap"] = (int64_t)r.bufs.capacity;
-    ctx->saved_data["n_local"] = (int64_t)r.bufs.n_local;
-    ctx->saved_data["layout"] = (int64_t)r.bufs.layout;
-    ctx->saved_data["cam_w"] = (int64_t)cam.width;
-    ctx->saved_data["cam_h"] = (int64_t)cam.height;
-    ctx->saved_data["cam_tx"] = (double)cam.tanfovx;
-    ctx->saved_data["cam_ty"] = (double)cam.tanfovy;
-    ctx->saved_data["cam_v"] = std::vector<double>(cam.viewmatrix.begin(), cam.viewmatrix.end());
-    ctx->saved_data["cam_p"] = std::vector<double>(cam.projmatrix.begin(), cam.projmatrix.end());
-    ctx->saved_data["cam_c"] = std::vector<double>(cam.campos.begin(), cam.campos.end());
-    ctx->saved_data["bg"] = std::vector<double>(rs.bg.begin(), rs.bg.end());
-    ctx->saved_data["smod"] = (double)rs.scale_modifier;
-    ctx->saved_data["D"] = (int64_t)rs.sh_degree;
-    ctx->saved_data["ty0"] = (int64_t)rs.tile_y0;
-    ctx->saved_data["ty1"] = (int64_t)rs.tile_y1;
-    ctx->saved_data["debug"] = rs.debug;
-    ctx->saved_data["max_rendered"] = (int64_t)rs.max_rendered;
-}
-
+// What both autograd Functions keep from forward to backward, and how backward gets it back
+// (floats as doubles, which hold them exactly).
 struct SavedFrame {
     RasterCamera cam;
     RasterSettings rs;
     int32_t K, cap, n_local;
     uint32_t layout;
+    bool has_m2d;
 };
 
+void save_frame(AutogradContext* ctx, const RasterCamera& cam, const RasterSettings& rs, const FwdResult& r,
+                const torch::Tensor& means2D) {
+    auto doubles = [](const auto& a) { return std::vector<double>(a.begin(), a.end()); };
+    // restore_frame reads the integers and the scalars back by position
+    ctx->saved_data["ints"] = std::vector<int64_t>{r.bufs.num_rendered, r.bufs.capacity, r.bufs.n_local, r.bufs.layout,
+                                                   present(means2D), cam.width, cam.height, rs.sh_degree, rs.tile_y0,
+                                                   rs.tile_y1, rs.debug, rs.max_rendered};
+    ctx->saved_data["scalars"] = std::vector<double>{cam.tanfovx, cam.tanfovy, rs.scale_modifier};
+    ctx->saved_data["cam_v"] = doubles(cam.viewmatrix);
+    ctx->saved_data["cam_p"] = doubles(cam.projmatrix);
+    ctx->saved_data["cam_c"] = doubles(cam.campos);
+    ctx->saved_data["bg"] = doubles(rs.bg);
+}
+
 SavedFrame restore_frame(AutogradContext* ctx) {
+    const auto n = ctx->saved_data["ints"].toIntVector();
+    const auto x = ctx->saved_data["scalars"].toDoubleVector();
+    auto floats = [&](const char* key, auto& dst) {
+        const auto v = ctx->saved_data[key].toDoubleVector();
+        for (size_t i = 0; i < dst.size(); ++i) dst[i] = (float)v[i];
+    };
     SavedFrame f;
-    RasterCamera& cam = f.cam;
-    cam.width = (int)ctx->saved_data["cam_w"].toInt();
-    cam.height = (int)ctx->saved_data["cam_h"].toInt();
-    cam.tanfovx = (float)ctx->saved_data["cam_tx"].toDouble();
-    cam.tanfovy = (float)ctx->saved_data["cam_ty"].toDouble();
-    auto V = ctx->saved_data["cam_v"].toDoubleVector();
-    auto Pm = ctx->saved_data["cam_p"].toDoubleVector();
-    auto C = ctx->saved_data["cam_c"].toDoubleVector();
-    for (int i = 0; i < 16; ++i) cam.viewmatrix[i] = (float)V[i], cam.projmatrix[i] = (float)Pm[i];
-    for (int i = 0; i < 3; ++i) cam.campos[i] = (float)C[i];
-    RasterSettings& rs = f.rs;
-    auto bg = ctx->saved_data["bg"].toDoubleVector();
-    for (int i = 0; i < 3; ++i) rs.bg[i] = (float)bg[i];
-    rs.scale_modifier = (float)ctx->saved_data["smod"].toDouble();
-    rs.sh_degree = (int)ctx->saved_data["D"].toInt();
-    rs.tile_y0 = (int)ctx->saved_data["ty0"].toInt();
-    rs.tile_y1 = (int)ctx->saved_data["ty1"].toInt();
-    rs.debug = ctx->saved_data["debug"].toBool();
-    rs.max_rendered = (int)ctx->saved_data["max_rendered"].toInt();
-    f.K = (int32_t)ctx->saved_data["K"].toInt();
-    f.cap = (int32_t)ctx->saved_data["cap"].toInt();
-    f.n_local = (int32_t)ctx->saved_data["n_local"].toInt();
-    f.layout = (uint32_t)ctx->saved_data["layout"].toInt();
+    f.K = (int32_t)n[0], f.cap = (int32_t)n[1], f.n_local = (int32_t)n[2], f.layout = (uint32_t)n[3];
+    f.has_m2d = n[4] != 0;
+    f.cam.width = (int)n[5], f.cam.height = (int)n[6];
+    f.rs.sh_degree = (int)n[7], f.rs.tile_y0 = (int)n[8], f.rs.tile_y1 = (int)n[9];
+    f.rs.debug = n[10] != 0, f.rs.max_rendered = (int)n[11];
+    f.cam.tanfovx = (float)x[0], f.cam.tanfovy = (float)x[1], f.rs.scale_modifier = (float)x[2];
+    floats("cam_v", f.cam.viewmatrix);
+    floats("cam_p", f.cam.projmatrix);
+    floats("cam_c", f.cam.campos);
+    floats("bg", f.rs.bg);
     return f;
 }
 
@@ -226,39 +212,89 @@ SavedFrame restore_frame(AutogradContext* ctx) {
 struct LeafGrads {
     torch::Tensor means2D, opac, means3D, dc, rest, colors, scales, rots, cov;
     gsr_grads gg{};
-    LeafGrads(const torch::Tensor& means3D_in, const torch::Tensor& sh_dc, const torch::Tensor& sh_rest,
-              const torch::Tensor& colors_in, const torch::Tensor& opac_in, const torch::Tensor& scales_in,
-              const torch::Tensor& rots_in, const torch::Tensor& cov3D) {
-        const int64_t P = means3D_in.size(0);
-        auto fo = means3D_in.options();
+    explicit LeafGrads(const Inputs& in) {
+        const int64_t P = in.means3D.size(0);
+        auto fo = in.means3D.options();
         means2D = torch::empty({P, 3}, fo);
-        opac = torch::empty_like(opac_in);
+        opac = torch::empty_like(in.opac);
         means3D = torch::empty({P, 3}, fo);
         gg.dL_dmeans2D = means2D.data_ptr<float>();
         gg.dL_dopacity = opac.data_ptr<float>();
         gg.dL_dmeans3D = means3D.data_ptr<float>();
-        if (present(colors_in)) {
-            colors = torch::empty_like(colors_in);
+        if (present(in.colors)) {
+            colors = torch::empty_like(in.colors);
             gg.dL_dcolors = colors.data_ptr<float>();
         } else {
-            dc = torch::empty_like(sh_dc);
+            dc = torch::empty_like(in.sh_dc);
             gg.dL_dsh_dc = dc.data_ptr<float>();
-            if (present(sh_rest)) {
-                rest = torch::empty_like(sh_rest);
+            if (present(in.sh_rest)) {
+                rest = torch::empty_like(in.sh_rest);
                 gg.dL_dsh_rest = rest.data_ptr<float>();
             }
         }
-        if (present(cov3D)) {
-            cov = torch::empty_like(cov3D);
+        if (present(in.cov3D)) {
+            cov = torch::empty_like(in.cov3D);
             gg.dL_dcov3D = cov.data_ptr<float>();
         } else {
-            scales = torch::empty_like(scales_in);
-            rots = torch::empty_like(rots_in);
+            scales = torch::empty_like(in.scales);
+            rots = torch::empty_like(in.rots);
             gg.dL_dscales = scales.data_ptr<float>();
             gg.dL_drotations = rots.data_ptr<float>();
         }
     }
 };
+
+// forward() of both autograd Functions: the render (inverse_depth != nullptr: with the depth and
+// alpha channels), everything backward needs, and the outputs {color, (depth, alpha,) radii, K on
+// the device, (K, capacity)}, all but the images non-differentiable.
+variable_list forward_and_save(AutogradContext* ctx, const RasterCamera& cam, const RasterSettings& rs,
+                               const bool* inverse_depth, const Inputs& in) {
+    const bool aux = inverse_depth != nullptr;
+    auto r = forward_impl(cam, rs, in, aux, aux && *inverse_depth);
+    ctx->save_for_backward({in.means3D, in.sh_dc, in.sh_rest, in.colors, in.opac, in.scales, in.rots, in.cov3D, r.geom,
+                            r.binning, r.image});
+    save_frame(ctx, cam, rs, r, in.means2D);
+    if (aux) ctx->saved_data["inverse_depth"] = *inverse_depth;
+    auto kdev = r.k_device();
+    auto kinfo = torch::tensor({r.bufs.num_rendered, r.bufs.capacity}, torch::kInt32);
+    ctx->mark_non_differentiable({r.radii, kdev, kinfo});
+    if (aux) return {r.color, r.depth, r.alpha, r.radii, kdev, kinfo};
+    return {r.color, r.radii, kdev, kinfo};
+}
+
+// backward() of both: the gradients of (means3D, means2D, sh_dc, sh_rest, colors, opac, scales,
+// rots, cov3D) from grad_out = {dL/dcolor} (gsr_backward), or with aux {dL/dcolor, dL/ddepth,
+// dL/dalpha} (gsr_backward_aux): an output the loss does not use arrives as an undefined gradient
+// and travels as NULL (= zero; the colour's as zeros).
+variable_list backward_saved(AutogradContext* ctx, const variable_list& grad_out, bool aux) {
+    const auto sv = ctx->get_saved_variables();  // forward_and_save's list
+    const Inputs in{sv[0], {}, sv[1], sv[2], sv[3], sv[4], sv[5], sv[6], sv[7]};
+    const SavedFrame f = restore_frame(ctx);
+    auto dL_dcolor = aux && !grad_out[0].defined() ? torch::zeros({3, f.cam.height, f.cam.width}, in.means3D.options())
+                                                   : grad_out[0].contiguous();
+    LeafGrads lg(in);
+    const gsr_camera c = f.cam.to_c();
+    const gsr_gaussians g = make_gaussians(f.rs, in);
+    gsr_raster_settings s = make_settings(f.rs);
+    const gsr_buffers b = buffers_of(sv[8], sv[9], sv[10], f.K, f.cap, f.n_local, f.layout);
+    AllocCtx scratch{in.means3D.device(), {}};
+    if (aux) {
+        torch::Tensor dL_ddepth, dL_dalpha;
+        if (grad_out[1].defined()) dL_ddepth = grad_out[1].contiguous();
+        if (grad_out[2].defined()) dL_dalpha = grad_out[2].contiguous();
+        s.flags |= GSR_FLAG_AUX | (ctx->saved_data["inverse_depth"].toBool() ? GSR_FLAG_INVDEPTH : 0u);
+        const gsr_aux_grads ag{dL_ddepth.defined() ? dL_ddepth.data_ptr<float>() : nullptr,
+                               dL_dalpha.defined() ? dL_dalpha.data_ptr<float>() : nullptr};
+        check(gsr_backward_aux(&c, &g, &s, &b, dL_dcolor.data_ptr<float>(), alloc_cb, &scratch, &lg.gg, cur_stream(),
+                               &ag),
+              "gsr_backward_aux");
+    } else {
+        check(gsr_backward(&c, &g, &s, &b, dL_dcolor.data_ptr<float>(), alloc_cb, &scratch, &lg.gg, cur_stream()),
+              "gsr_backward");
+    }
+    if (!f.has_m2d) lg.means2D = torch::Tensor();
+    return {lg.means3D, lg.means2D, lg.dc, lg.rest, lg.colors, lg.opac, lg.scales, lg.rots, lg.cov};
+}
 
 class RasterizeGaussians : public torch::autograd::Function<RasterizeGaussians> {
    public:
@@ -266,87 +302,49 @@ class RasterizeGaussians : public torch::autograd::Function<RasterizeGaussians> 
                                  torch::Tensor means3D, torch::Tensor means2D, torch::Tensor sh_dc,
                                  torch::Tensor sh_rest, torch::Tensor colors, torch::Tensor opac,
                                  torch::Tensor scales, torch::Tensor rots, torch::Tensor cov3D) {
-        auto r = forward_impl(cam, rs, means3D, sh_dc, sh_rest, colors, opac, scales, rots, cov3D);
-        ctx->save_for_backward({means3D, sh_dc, sh_rest, colors, opac, scales, rots, cov3D, r.geom, r.binning,
-                                r.image});
-        save_frame(ctx, cam, rs, r, means2D);
-        auto kdev = r.k_device();
-        auto kinfo = torch::tensor({r.bufs.num_rendered, r.bufs.capacity}, torch::kInt32);
-        ctx->mark_non_differentiable({r.radii, kdev, kinfo});
-        return {r.color, r.radii, kdev, kinfo};
+        return forward_and_save(ctx, cam, rs, nullptr,
+                                {means3D, means2D, sh_dc, sh_rest, colors, opac, scales, rots, cov3D});
     }
 
     static variable_list backward(AutogradContext* ctx, variable_list grad_out) {
-        auto sv = ctx->get_saved_variables();
-        auto means3D = sv[0], sh_dc = sv[1], sh_rest = sv[2], colors = sv[3], opac = sv[4], scales = sv[5],
-             rots = sv[6], cov3D = sv[7], geom = sv[8], binning = sv[9], image = sv[10];
-        const SavedFrame f = restore_frame(ctx);
-        auto dL_dcolor = grad_out[0].contiguous();
-        LeafGrads lg(means3D, sh_dc, sh_rest, colors, opac, scales, rots, cov3D);
-        const gsr_camera c = f.cam.to_c();
-        const gsr_gaussians g = make_gaussians(f.rs, means3D, sh_dc, sh_rest, colors, opac, scales, rots, cov3D);
-        const gsr_raster_settings s = make_settings(f.rs);
-        const gsr_buffers b = buffers_of(geom, binning, image, f.K, f.cap, f.n_local, f.layout);
-        AllocCtx scratch{means3D.device(), {}};
-        check(gsr_backward(&c, &g, &s, &b, dL_dcolor.data_ptr<float>(), alloc_cb, &scratch, &lg.gg, cur_stream()),
-              "gsr_backward");
-        // inputs of forward(): cam, rs, means3D, means2D, sh_dc, sh_rest, colors, opac, scales, rots, cov3D
-        if (!ctx->saved_data["has_m2d"].toBool()) lg.means2D = torch::Tensor();
-        return {torch::Tensor(), torch::Tensor(), lg.means3D, lg.means2D, lg.dc, lg.rest, lg.colors, lg.opac,
-                lg.scales, lg.rots, lg.cov};
+        variable_list g = backward_saved(ctx, grad_out, false);
+        g.insert(g.begin(), 2, torch::Tensor());  // cam, rs
+        return g;
     }
 };
 
 // RasterizeGaussians with the depth and alpha outputs (gsr_forward_aux / gsr_backward_aux): one
-// forward, one backward for a loss over colour, depth and alpha.  An output the loss does not use
-// arrives as an undefined gradient and travels as NULL (= zero).
+// forward, one backward for a loss over colour, depth and alpha.
 class RasterizeGaussiansAux : public torch::autograd::Function<RasterizeGaussiansAux> {
    public:
     static variable_list forward(AutogradContext* ctx, const RasterCamera& cam, const RasterSettings& rs,
                                  bool inverse_depth, torch::Tensor means3D, torch::Tensor means2D,
                                  torch::Tensor sh_dc, torch::Tensor sh_rest, torch::Tensor colors, torch::Tensor opac,
                                  torch::Tensor scales, torch::Tensor rots, torch::Tensor cov3D) {
-        auto r = forward_impl(cam, rs, means3D, sh_dc, sh_rest, colors, opac, scales, rots, cov3D, true,
-                              inverse_depth);
-        ctx->save_for_backward({means3D, sh_dc, sh_rest, colors, opac, scales, rots, cov3D, r.geom, r.binning,
-                                r.image});
-        save_frame(ctx, cam, rs, r, means2D);
-        ctx->saved_data["inverse_depth"] = inverse_depth;
-        auto kdev = r.k_device();
-        auto kinfo = torch::tensor({r.bufs.num_rendered, r.bufs.capacity}, torch::kInt32);
-        ctx->mark_non_differentiable({r.radii, kdev, kinfo});
-        return {r.color, r.depth, r.alpha, r.radii, kdev, kinfo};
+        return forward_and_save(ctx, cam, rs, &inverse_depth,
+                                {means3D, means2D, sh_dc, sh_rest, colors, opac, scales, rots, cov3D});
     }
 
     static variable_list backward(AutogradContext* ctx, variable_list grad_out) {
-        auto sv = ctx->get_saved_variables();
-        auto means3D = sv[0], sh_dc = sv[1], sh_rest = sv[2], colors = sv[3], opac = sv[4], scales = sv[5],
-             rots = sv[6], cov3D = sv[7], geom = sv[8], binning = sv[9], image = sv[10];
-        const SavedFrame f = restore_frame(ctx);
-        auto dL_dcolor = grad_out[0].defined()
-                             ? grad_out[0].contiguous()
-                             : torch::zeros({3, f.cam.height, f.cam.width}, means3D.options());
-        torch::Tensor dL_ddepth, dL_dalpha;
-        if (grad_out[1].defined()) dL_ddepth = grad_out[1].contiguous();
-        if (grad_out[2].defined()) dL_dalpha = grad_out[2].contiguous();
-        LeafGrads lg(means3D, sh_dc, sh_rest, colors, opac, scales, rots, cov3D);
-        const gsr_camera c = f.cam.to_c();
-        const gsr_gaussians g = make_gaussians(f.rs, means3D, sh_dc, sh_rest, colors, opac, scales, rots, cov3D);
-        gsr_raster_settings s = make_settings(f.rs);
-        s.flags |= GSR_FLAG_AUX | (ctx->saved_data["inverse_depth"].toBool() ? GSR_FLAG_INVDEPTH : 0u);
-        const gsr_buffers b = buffers_of(geom, binning, image, f.K, f.cap, f.n_local, f.layout);
-        const gsr_aux_grads ag{dL_ddepth.defined() ? dL_ddepth.data_ptr<float>() : nullptr,
-                               dL_dalpha.defined() ? dL_dalpha.data_ptr<float>() : nullptr};
-        AllocCtx scratch{means3D.device(), {}};
-        check(gsr_backward_aux(&c, &g, &s, &b, dL_dcolor.data_ptr<float>(), alloc_cb, &scratch, &lg.gg, cur_stream(),
-                               &ag),
-              "gsr_backward_aux");
-        // inputs of forward(): cam, rs, inverse_depth, means3D, means2D, sh_dc, sh_rest, colors, opac, scales, ...
-        if (!ctx->saved_data["has_m2d"].toBool()) lg.means2D = torch::Tensor();
-        return {torch::Tensor(), torch::Tensor(), torch::Tensor(), lg.means3D, lg.means2D, lg.dc, lg.rest, lg.colors,
-                lg.opac, lg.scales, lg.rots, lg.cov};
+        variable_list g = backward_saved(ctx, grad_out, true);
+        g.insert(g.begin(), 3, torch::Tensor());  // cam, rs, inverse_depth
+        return g;
     }
 };
+
+// Both rasterize_gaussians entry points (inverse_depth != nullptr: the aux Function).  Absent
+// optional inputs go in as defined 0-element tensors (see present()).
+std::vector<torch::Tensor> rasterize(const RasterCamera& cam, const RasterSettings& rs, const bool* inverse_depth,
+                                     Inputs in) {
+    auto none = torch::empty({0}, in.means3D.options());
+    for (torch::Tensor* t : {&in.means2D, &in.sh_dc, &in.sh_rest, &in.colors, &in.scales, &in.rots, &in.cov3D})
+        if (!t->defined()) *t = none;
+    if (inverse_depth)
+        return RasterizeGaussiansAux::apply(cam, rs, *inverse_depth, in.means3D, in.means2D, in.sh_dc, in.sh_rest,
+                                            in.colors, in.opac, in.scales, in.rots, in.cov3D);
+    return RasterizeGaussians::apply(cam, rs, in.means3D, in.means2D, in.sh_dc, in.sh_rest, in.colors, in.opac,
+                                     in.scales, in.rots, in.cov3D);
+}
 
 }  // namespace
 
@@ -363,14 +361,14 @@ Frame forward(const RasterCamera& cam, const RasterSettings& rs, const torch::Te
               const torch::Tensor& sh_dc, const torch::Tensor& sh_rest, const torch::Tensor& colors,
               const torch::Tensor& opac, const torch::Tensor& scales, const torch::Tensor& rots,
               const torch::Tensor& cov3D) {
-    return forward_impl(cam, rs, means3D, sh_dc, sh_rest, colors, opac, scales, rots, cov3D);
+    return forward_impl(cam, rs, {means3D, {}, sh_dc, sh_rest, colors, opac, scales, rots, cov3D});
 }
 
 void backward(const Frame& f, const RasterSettings& rs, const torch::Tensor& means3D, const torch::Tensor& sh_dc,
               const torch::Tensor& sh_rest, const torch::Tensor& colors, const torch::Tensor& opac,
               const torch::Tensor& scales, const torch::Tensor& rots, const torch::Tensor& cov3D,
               const torch::Tensor& dL_dcolor, const gsr_grads& grads) {
-    const gsr_gaussians g = make_gaussians(rs, means3D, sh_dc, sh_rest, colors, opac, scales, rots, cov3D);
+    const gsr_gaussians g = make_gaussians(rs, {means3D, {}, sh_dc, sh_rest, colors, opac, scales, rots, cov3D});
     TORCH_CHECK(dL_dcolor.is_contiguous() && dL_dcolor.numel() == 3LL * f.cam.width * f.cam.height,
                 "dL_dcolor must be a contiguous (3,H,W) tensor");
     AllocCtx scratch{means3D.device(), {}};
@@ -507,10 +505,7 @@ std::vector<torch::Tensor> rasterize_gaussians(const RasterCamera& cam, const Ra
                                                const torch::Tensor& colors, const torch::Tensor& opac,
                                                const torch::Tensor& scales, const torch::Tensor& rots,
                                                const torch::Tensor& cov3D) {
-    auto none = torch::empty({0}, means3D.options());
-    auto opt_in = [&](const torch::Tensor& t) { return t.defined() ? t : none; };
-    return RasterizeGaussians::apply(cam, rs, means3D, opt_in(means2D), opt_in(sh_dc), opt_in(sh_rest),
-                                     opt_in(colors), opac, opt_in(scales), opt_in(rots), opt_in(cov3D));
+    return rasterize(cam, rs, nullptr, {means3D, means2D, sh_dc, sh_rest, colors, opac, scales, rots, cov3D});
 }
 
 std::vector<torch::Tensor> rasterize_gaussians_aux(const RasterCamera& cam, const RasterSettings& rs,
@@ -519,11 +514,7 @@ std::vector<torch::Tensor> rasterize_gaussians_aux(const RasterCamera& cam, cons
                                                    const torch::Tensor& sh_rest, const torch::Tensor& colors,
                                                    const torch::Tensor& opac, const torch::Tensor& scales,
                                                    const torch::Tensor& rots, const torch::Tensor& cov3D) {
-    auto none = torch::empty({0}, means3D.options());
-    auto opt_in = [&](const torch::Tensor& t) { return t.defined() ? t : none; };
-    return RasterizeGaussiansAux::apply(cam, rs, inverse_depth, means3D, opt_in(means2D), opt_in(sh_dc),
-                                        opt_in(sh_rest), opt_in(colors), opac, opt_in(scales), opt_in(rots),
-                                        opt_in(cov3D));
+    return rasterize(cam, rs, &inverse_depth, {means3D, means2D, sh_dc, sh_rest, colors, opac, scales, rots, cov3D});
 }
 
 torch::Tensor eval_sh_colors(int D, const torch::Tensor& sh, const torch::Tensor& dirs) {
@@ -589,7 +580,8 @@ static gsr::RasterSettings settings_from_py(const std::vector<float>& bg, float 
     return rs;
 }
 
-static torch::Tensor opt(const c10::optional<torch::Tensor>& t) { return t.has_value() ? *t : torch::Tensor(); }
+using OptTensor = c10::optional<torch::Tensor>;
+static torch::Tensor opt(const OptTensor& t) { return t.has_value() ? *t : torch::Tensor(); }
 
 namespace gsr {
 void bind_shard(pybind11::module& m);  // gsr_shard.cpp
@@ -613,12 +605,11 @@ PYBIND11_MODULE(_gsr_torch, m) {
              py::arg("debug") = false, py::arg("max_rendered") = 0);
     m.def(
         "rasterize_gaussians",
-        [](const gsr::RasterCamera& cam, const gsr::RasterSettings& rs, torch::Tensor means3D,
-           torch::Tensor means2D, c10::optional<torch::Tensor> sh_dc, c10::optional<torch::Tensor> sh_rest,
-           c10::optional<torch::Tensor> colors, torch::Tensor opac, c10::optional<torch::Tensor> scales,
-           c10::optional<torch::Tensor> rots, c10::optional<torch::Tensor> cov3D) {
-            auto r = gsr::rasterize_gaussians(cam, rs, means3D, means2D, opt(sh_dc), opt(sh_rest), opt(colors),
-                                              opac, opt(scales), opt(rots), opt(cov3D));
+        [](const gsr::RasterCamera& cam, const gsr::RasterSettings& rs, torch::Tensor means3D, torch::Tensor means2D,
+           OptTensor sh_dc, OptTensor sh_rest, OptTensor colors, torch::Tensor opac, OptTensor scales, OptTensor rots,
+           OptTensor cov3D) {
+            auto r = gsr::rasterize(cam, rs, nullptr, {means3D, means2D, opt(sh_dc), opt(sh_rest), opt(colors), opac,
+                                                       opt(scales), opt(rots), opt(cov3D)});
             return py::make_tuple(r[0], r[1]);
         },
         py::arg("cam"), py::arg("settings"), py::arg("means3D"), py::arg("means2D"), py::arg("sh_dc"),
@@ -627,11 +618,10 @@ PYBIND11_MODULE(_gsr_torch, m) {
     m.def(
         "rasterize_gaussians_aux",
         [](const gsr::RasterCamera& cam, const gsr::RasterSettings& rs, bool inverse_depth, torch::Tensor means3D,
-           torch::Tensor means2D, c10::optional<torch::Tensor> sh_dc, c10::optional<torch::Tensor> sh_rest,
-           c10::optional<torch::Tensor> colors, torch::Tensor opac, c10::optional<torch::Tensor> scales,
-           c10::optional<torch::Tensor> rots, c10::optional<torch::Tensor> cov3D) {
-            auto r = gsr::rasterize_gaussians_aux(cam, rs, inverse_depth, means3D, means2D, opt(sh_dc), opt(sh_rest),
-                                                  opt(colors), opac, opt(scales), opt(rots), opt(cov3D));
+           torch::Tensor means2D, OptTensor sh_dc, OptTensor sh_rest, OptTensor colors, torch::Tensor opac,
+           OptTensor scales, OptTensor rots, OptTensor cov3D) {
+            auto r = gsr::rasterize(cam, rs, &inverse_depth, {means3D, means2D, opt(sh_dc), opt(sh_rest), opt(colors),
+                                                              opac, opt(scales), opt(rots), opt(cov3D)});
             return py::make_tuple(r[0], r[1], r[2], r[3]);
         },
         py::arg("cam"), py::arg("settings"), py::arg("inverse_depth"), py::arg("means3D"), py::arg("means2D"),

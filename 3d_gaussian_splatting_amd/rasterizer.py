@@ -64,29 +64,19 @@ class _Allocator:
         return t.data_ptr()
 
 
-@dataclass
-class ForwardState:
-    cam: RasterCamera
-    inputs: dict
-    settings: native.Settings
-    gauss: native.Gaussians
-    buffers: native.Buffers
-    color: torch.Tensor
-    radii: torch.Tensor
-    allocs: list = field(default_factory=list)
-    depth: torch.Tensor | None = None   # forward_aux: (H, W) sum w v (v = z, or 1 / z)
-    alpha: torch.Tensor | None = None   # forward_aux: (H, W) sum w = 1 - final T
+class _CallState:
+    """What a forward's state object can ask the library afterwards.  The subclass names the camera
+    struct and the entry count the library was called with: `_call_camera()`, `_call_entries()`."""
 
     @property
     def num_rendered(self) -> int:
         """K.  Under a binning bound (max_rendered > 0) K stays on the device until asked for:
         the first access reads it back (synchronising the stream) and raises on an overflow."""
         if self.buffers.num_rendered < 0:
-            L = native.load_hip()
-            c = native.camera_struct(self.cam)
             k = ctypes.c_int32(0)
-            rc = L.gsr_read_num_rendered(ctypes.byref(c), ctypes.byref(self.buffers), ctypes.byref(k),
-                                         ctypes.c_void_p(torch.cuda.current_stream(self.color.device).cuda_stream))
+            rc = native.load_hip().gsr_read_num_rendered(
+                ctypes.byref(self._call_camera()), ctypes.byref(self.buffers), ctypes.byref(k),
+                ctypes.c_void_p(torch.cuda.current_stream(self.color.device).cuda_stream))
             if rc == native.GSR_ERR_OVERFLOW:
                 raise OverflowError(native.last_error())
             if rc != 0:
@@ -102,21 +92,13 @@ class ForwardState:
                     return t, ptr - base
         raise KeyError("pointer not inside a forward buffer")
 
-    def k_device(self) -> torch.Tensor:
-        """K as a 1-element int32 device tensor aliasing the scan's counter (no copy, no sync)."""
-        L = native.load_hip()
-        c = native.camera_struct(self.cam)
-        p = L.gsr_view(ctypes.byref(c), self.gauss.P, ctypes.byref(self.buffers), native.VIEW_COUNTS)
-        if not p:
-            raise RuntimeError("gsr_view(COUNTS) returned NULL")
-        t, off = self._owner(p)
-        return t[off:off + 4].view(torch.int32)
+    def _view_ptr(self, what: int):
+        return native.load_hip().gsr_view(ctypes.byref(self._call_camera()), self._call_entries(),
+                                          ctypes.byref(self.buffers), what)
 
     def view(self, what: int, dtype: torch.dtype, count: int) -> torch.Tensor:
         """Copy of an internal array (gsr_view) as a torch tensor."""
-        L = native.load_hip()
-        c = native.camera_struct(self.cam)
-        p = L.gsr_view(ctypes.byref(c), self.gauss.P, ctypes.byref(self.buffers), what)
+        p = self._view_ptr(what)
         if not p or count == 0:
             return torch.empty(0, dtype=dtype, device=self.color.device)
         t, off = self._owner(p)
@@ -125,8 +107,38 @@ class ForwardState:
 
 
 @dataclass
-class ViewsState:
-    """gsr_forward_views' outputs, kept for gsr_backward_views (one set of buffers for all views)."""
+class ForwardState(_CallState):
+    cam: RasterCamera
+    inputs: dict
+    settings: native.Settings
+    gauss: native.Gaussians
+    buffers: native.Buffers
+    color: torch.Tensor
+    radii: torch.Tensor
+    allocs: list = field(default_factory=list)
+    depth: torch.Tensor | None = None   # forward_aux: (H, W) sum w v (v = z, or 1 / z)
+    alpha: torch.Tensor | None = None   # forward_aux: (H, W) sum w = 1 - final T
+
+    def _call_camera(self):
+        return native.camera_struct(self.cam)
+
+    def _call_entries(self) -> int:
+        return self.gauss.P
+
+    def k_device(self) -> torch.Tensor:
+        """K as a 1-element int32 device tensor aliasing the scan's counter (no copy, no sync)."""
+        p = self._view_ptr(native.VIEW_COUNTS)
+        if not p:
+            raise RuntimeError("gsr_view(COUNTS) returned NULL")
+        t, off = self._owner(p)
+        return t[off:off + 4].view(torch.int32)
+
+
+@dataclass
+class ViewsState(_CallState):
+    """gsr_forward_views' outputs, kept for gsr_backward_views (one set of buffers for all views).
+    num_rendered is K over all views; view() sees the tall grid and the V * P (view, Gaussian)
+    entries e = v * P + g: sorted tiles are tall-grid tile ids, sorted gids are entry ids."""
     cams: list
     cstructs: object          # the gsr_camera array handed to the library
     inputs: dict
@@ -137,26 +149,6 @@ class ViewsState:
     radii: torch.Tensor       # V x P
     allocs: list
 
-    @property
-    def num_rendered(self) -> int:
-        """K over all views.  Under a binning bound (max_rendered > 0) it is read back on first
-        access through gsr_read_num_rendered with the pass's tall camera (the views stacked as
-        bands of ceil(H / 16) tile rows), raising on an overflow."""
-        if self.buffers.num_rendered < 0:
-            L = native.load_hip()
-            tall = native.Camera()
-            ctypes.memmove(ctypes.byref(tall), ctypes.byref(self.cstructs[0]), ctypes.sizeof(tall))
-            tall.height = len(self.cams) * ((self.cams[0].height + 15) // 16) * 16
-            k = ctypes.c_int32(0)
-            rc = L.gsr_read_num_rendered(ctypes.byref(tall), ctypes.byref(self.buffers), ctypes.byref(k),
-                                         ctypes.c_void_p(torch.cuda.current_stream(self.color.device).cuda_stream))
-            if rc == native.GSR_ERR_OVERFLOW:
-                raise OverflowError(native.last_error())
-            if rc != 0:
-                raise RuntimeError(f"gsr_read_num_rendered failed ({rc}): {native.last_error()}")
-            self.buffers.num_rendered = k.value
-        return int(self.buffers.num_rendered)
-
     def tall_camera(self):
         """The pass's camera struct: the views stacked as bands of ceil(H / 16) tile rows."""
         tall = native.Camera()
@@ -164,22 +156,10 @@ class ViewsState:
         tall.height = len(self.cams) * ((self.cams[0].height + 15) // 16) * 16
         return tall
 
-    def view(self, what: int, dtype: torch.dtype, count: int) -> torch.Tensor:
-        """Copy of an internal array of the pass (gsr_view over the tall grid and the V * P
-        (view, Gaussian) entries e = v * P + g): sorted tiles are tall-grid tile ids, sorted gids
-        are entry ids."""
-        L = native.load_hip()
-        tall = self.tall_camera()
-        p = L.gsr_view(ctypes.byref(tall), len(self.cams) * self.gauss.P, ctypes.byref(self.buffers), what)
-        if not p or count == 0:
-            return torch.empty(0, dtype=dtype, device=self.color.device)
-        nbytes = count * torch.empty(0, dtype=dtype).element_size()
-        for a in self.allocs:
-            for t in a.tensors:
-                base = t.data_ptr()
-                if base <= p < base + t.numel():
-                    return t[p - base:p - base + nbytes].view(dtype).clone()
-        raise KeyError("pointer not inside a views buffer")
+    _call_camera = tall_camera
+
+    def _call_entries(self) -> int:
+        return len(self.cams) * self.gauss.P
 
 
 class CAbiRasterizer:
@@ -246,27 +226,36 @@ class CAbiRasterizer:
         s.max_rendered = int(max_rendered)
         return inputs, g, s
 
+    def _forward(self, cam: RasterCamera, inverse_depth, *prep) -> ForwardState:
+        """gsr_forward, or gsr_forward_aux when inverse_depth is not None; prep: _prepare's arguments."""
+        dev = self.device
+        inputs, g, s = self._prepare(*prep)
+        P, H, W = g.P, cam.height, cam.width
+        color = torch.empty((3, H, W), dtype=torch.float32, device=dev)
+        radii = torch.empty((P,), dtype=torch.int32, device=dev)
+        ag, ab, ai = _Allocator(dev), _Allocator(dev), _Allocator(dev)
+        bufs = native.Buffers()
+        args = (ctypes.byref(self._cam(cam)), ctypes.byref(g), ctypes.byref(s), _ptr(color),
+                _ptr(radii) if P else None, ag.cb, ab.cb, ai.cb, None, ctypes.byref(bufs), self._stream())
+        depth = alpha = None
+        if inverse_depth is None:
+            self._check(self.L.gsr_forward(*args), "gsr_forward")
+        else:
+            s.flags |= native.GSR_FLAG_AUX | (native.GSR_FLAG_INVDEPTH if inverse_depth else 0)
+            depth = torch.empty((H, W), dtype=torch.float32, device=dev)
+            alpha = torch.empty((H, W), dtype=torch.float32, device=dev)
+            aux = native.AuxOut(depth.data_ptr(), alpha.data_ptr())
+            self._check(self.L.gsr_forward_aux(*args, ctypes.byref(aux)), "gsr_forward_aux")
+        return ForwardState(cam=cam, inputs=inputs, settings=s, gauss=g, buffers=bufs, color=color,
+                            radii=radii, allocs=[ag, ab, ai], depth=depth, alpha=alpha)
+
     def forward(self, cam: RasterCamera, means3D, opacities, scales=None, rotations=None, sh_dc=None,
                 sh_rest=None, sh_degree=0, colors_precomp=None, cov3D_precomp=None, scale_modifier=1.0,
                 bg=(0.0, 0.0, 0.0), tile_rows=None, max_rendered=0, debug=False) -> ForwardState:
         """gsr_forward.  max_rendered > 0 sizes the binning for that many instances and skips the
         host read of K (see ForwardState.num_rendered)."""
-        dev = self.device
-        inputs, g, s = self._prepare(means3D, opacities, scales, rotations, sh_dc, sh_rest, sh_degree,
-                                     colors_precomp, cov3D_precomp, scale_modifier, bg, tile_rows, max_rendered,
-                                     debug)
-        P = g.P
-        color = torch.empty((3, cam.height, cam.width), dtype=torch.float32, device=dev)
-        radii = torch.empty((P,), dtype=torch.int32, device=dev)
-        ag, ab, ai = _Allocator(dev), _Allocator(dev), _Allocator(dev)
-        bufs = native.Buffers()
-        c = self._cam(cam)
-        rc = self.L.gsr_forward(ctypes.byref(c), ctypes.byref(g), ctypes.byref(s), _ptr(color),
-                                _ptr(radii) if P else None, ag.cb, ab.cb, ai.cb, None, ctypes.byref(bufs),
-                                self._stream())
-        self._check(rc, "gsr_forward")
-        return ForwardState(cam=cam, inputs=inputs, settings=s, gauss=g, buffers=bufs, color=color,
-                            radii=radii, allocs=[ag, ab, ai])
+        return self._forward(cam, None, means3D, opacities, scales, rotations, sh_dc, sh_rest, sh_degree,
+                             colors_precomp, cov3D_precomp, scale_modifier, bg, tile_rows, max_rendered, debug)
 
     def forward_aux(self, cam: RasterCamera, means3D, opacities, scales=None, rotations=None, sh_dc=None,
                     sh_rest=None, sh_degree=0, colors_precomp=None, cov3D_precomp=None, scale_modifier=1.0,
@@ -274,42 +263,32 @@ class CAbiRasterizer:
                     inverse_depth=False) -> ForwardState:
         """gsr_forward_aux: forward() plus .depth = sum w z (sum w / z with inverse_depth) and
         .alpha = sum w per pixel, over the pairs the colour pass blends.  Full images only."""
-        dev = self.device
-        inputs, g, s = self._prepare(means3D, opacities, scales, rotations, sh_dc, sh_rest, sh_degree,
-                                     colors_precomp, cov3D_precomp, scale_modifier, bg, tile_rows, max_rendered,
-                                     debug)
-        s.flags |= native.GSR_FLAG_AUX | (native.GSR_FLAG_INVDEPTH if inverse_depth else 0)
-        P = g.P
-        color = torch.empty((3, cam.height, cam.width), dtype=torch.float32, device=dev)
-        depth = torch.empty((cam.height, cam.width), dtype=torch.float32, device=dev)
-        alpha = torch.empty((cam.height, cam.width), dtype=torch.float32, device=dev)
-        radii = torch.empty((P,), dtype=torch.int32, device=dev)
-        ag, ab, ai = _Allocator(dev), _Allocator(dev), _Allocator(dev)
-        bufs = native.Buffers()
-        aux = native.AuxOut(depth.data_ptr(), alpha.data_ptr())
-        c = self._cam(cam)
-        rc = self.L.gsr_forward_aux(ctypes.byref(c), ctypes.byref(g), ctypes.byref(s), _ptr(color),
-                                    _ptr(radii) if P else None, ag.cb, ab.cb, ai.cb, None, ctypes.byref(bufs),
-                                    self._stream(), ctypes.byref(aux))
-        self._check(rc, "gsr_forward_aux")
-        return ForwardState(cam=cam, inputs=inputs, settings=s, gauss=g, buffers=bufs, color=color,
-                            radii=radii, allocs=[ag, ab, ai], depth=depth, alpha=alpha)
+        return self._forward(cam, bool(inverse_depth), means3D, opacities, scales, rotations, sh_dc, sh_rest,
+                             sh_degree, colors_precomp, cov3D_precomp, scale_modifier, bg, tile_rows, max_rendered,
+                             debug)
+
+    def _backward(self, st: ForwardState, dL_dpix, aux_grads=None) -> dict:
+        """gsr_backward, or gsr_backward_aux with aux_grads = (dL_ddepth, dL_dalpha), each None = zero."""
+        H, W = st.cam.height, st.cam.width
+        dpix = _f32(dL_dpix, (3, H, W), self.device)
+        out, gg = self._grad_tensors(st)
+        scratch = _Allocator(self.device)
+        args = (ctypes.byref(self._cam(st.cam)), ctypes.byref(st.gauss), ctypes.byref(st.settings),
+                ctypes.byref(st.buffers), _ptr(dpix), scratch.cb, None, ctypes.byref(gg), self._stream())
+        if aux_grads is None:
+            self._check(self.L.gsr_backward(*args), "gsr_backward")
+        else:
+            dd, da = (_f32(t, (H, W), self.device) for t in aux_grads)
+            aux = native.AuxGrads(None if dd is None else dd.data_ptr(), None if da is None else da.data_ptr())
+            self._check(self.L.gsr_backward_aux(*args, ctypes.byref(aux)), "gsr_backward_aux")
+        return out
+
+    def backward(self, st: ForwardState, dL_dpix) -> dict:
+        return self._backward(st, dL_dpix)
 
     def backward_aux(self, st: ForwardState, dL_dpix, dL_ddepth=None, dL_dalpha=None) -> dict:
         """gsr_backward_aux: backward() for a loss over colour, depth and alpha (None = zero)."""
-        H, W = st.cam.height, st.cam.width
-        dpix = _f32(dL_dpix, (3, H, W), self.device)
-        dd = _f32(dL_ddepth, (H, W), self.device)
-        da = _f32(dL_dalpha, (H, W), self.device)
-        out, gg = self._grad_tensors(st)
-        scratch = _Allocator(self.device)
-        aux = native.AuxGrads(None if dd is None else dd.data_ptr(), None if da is None else da.data_ptr())
-        c = self._cam(st.cam)
-        rc = self.L.gsr_backward_aux(ctypes.byref(c), ctypes.byref(st.gauss), ctypes.byref(st.settings),
-                                     ctypes.byref(st.buffers), _ptr(dpix), scratch.cb, None, ctypes.byref(gg),
-                                     self._stream(), ctypes.byref(aux))
-        self._check(rc, "gsr_backward_aux")
-        return out
+        return self._backward(st, dL_dpix, (dL_ddepth, dL_dalpha))
 
     def forward_batch(self, cams, means3D, opacities, scales=None, rotations=None, sh_dc=None, sh_rest=None,
                       sh_degree=0, colors_precomp=None, cov3D_precomp=None, scale_modifier=1.0,
@@ -400,17 +379,6 @@ class CAbiRasterizer:
         for k, v in out.items():
             setattr(gg, names[k], v.data_ptr())
         return out, gg
-
-    def backward(self, st: ForwardState, dL_dpix) -> dict:
-        dpix = _f32(dL_dpix, (3, st.cam.height, st.cam.width), self.device)
-        out, gg = self._grad_tensors(st)
-        scratch = _Allocator(self.device)
-        c = self._cam(st.cam)
-        rc = self.L.gsr_backward(ctypes.byref(c), ctypes.byref(st.gauss), ctypes.byref(st.settings),
-                                 ctypes.byref(st.buffers), _ptr(dpix), scratch.cb, None, ctypes.byref(gg),
-                                 self._stream())
-        self._check(rc, "gsr_backward")
-        return out
 
     def backward_blend(self, st: ForwardState, dL_dpix, out: torch.Tensor | None = None) -> torch.Tensor:
         """B1 + per-Gaussian sum -> grad2d (P x 12).  `out`: optional contiguous (>= P) x 12
@@ -597,6 +565,12 @@ def ext_camera(cam: RasterCamera):
                             [float(v) for v in cam.campos])
 
 
+def _ext_settings(ext, bg, scale_modifier, sh_degree, tile_rows, debug, max_rendered):
+    y0, y1 = (0, INT32_MAX) if tile_rows is None else tile_rows
+    return ext.RasterSettings([float(v) for v in bg], float(scale_modifier), int(sh_degree), int(y0), int(y1),
+                              bool(debug), int(max_rendered))
+
+
 def rasterize_gaussians_aux(cam: RasterCamera, means3D, means2D, opacities, sh_dc=None, sh_rest=None,
                             colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None,
                             sh_degree=0, scale_modifier=1.0, bg=(0.0, 0.0, 0.0), tile_rows=None, debug=False,
@@ -605,9 +579,7 @@ def rasterize_gaussians_aux(cam: RasterCamera, means3D, means2D, opacities, sh_d
     int32).  color, depth and alpha are differentiable in every tensor input; depth = sum w z
     (sum w / z with inverse_depth), alpha = sum w, un-normalised (expected depth = depth / alpha)."""
     ext = native.load_torch_ext()
-    y0, y1 = (0, INT32_MAX) if tile_rows is None else tile_rows
-    rs = ext.RasterSettings([float(v) for v in bg], float(scale_modifier), int(sh_degree), int(y0), int(y1),
-                            bool(debug), int(max_rendered))
+    rs = _ext_settings(ext, bg, scale_modifier, sh_degree, tile_rows, debug, max_rendered)
     return ext.rasterize_gaussians_aux(ext_camera(cam), rs, bool(inverse_depth), means3D, means2D, sh_dc, sh_rest,
                                        colors_precomp, opacities, scales, rotations, cov3D_precomp)
 
@@ -619,9 +591,7 @@ def rasterize_gaussians(cam: RasterCamera, means3D, means2D, opacities, sh_dc=No
     """RasterizeGaussians.apply: returns (color (3,H,W), radii (P,) int32); differentiable in
     every tensor input (means2D receives the screen-space gradient)."""
     ext = native.load_torch_ext()
-    y0, y1 = (0, INT32_MAX) if tile_rows is None else tile_rows
-    rs = ext.RasterSettings([float(v) for v in bg], float(scale_modifier), int(sh_degree), int(y0), int(y1),
-                            bool(debug), int(max_rendered))
+    rs = _ext_settings(ext, bg, scale_modifier, sh_degree, tile_rows, debug, max_rendered)
     return ext.rasterize_gaussians(ext_camera(cam), rs, means3D, means2D, sh_dc, sh_rest, colors_precomp,
                                    opacities, scales, rotations, cov3D_precomp)
 

@@ -124,7 +124,18 @@ def test_depth_only_loss(inverse, case1, rast, oracle):
 
 
 # ---- case 2: large-image path (4096 tiles: two-wave F6 at 7 waves per SIMD, plain-loop B1) ----
-def test_parity_large_image(rast, oracle):
+@pytest.fixture(scope="module")
+def case2():
+    gr, sc = pkg("graphics"), pkg("scene")
+    cam = gr.synthetic_camera(1024, 1024)
+    assert cam.grid[0] * cam.grid[1] == 4096
+    s = sc.make_scene(cam, 20000, max_sh_degree=3, seed=5)
+    dC = sc.make_dL_dpix(cam, seed=6)
+    dD, dA = make_aux_grads(cam, seed=7)
+    return cam, _scene_inputs(s), dC, dD, dA
+
+
+def test_parity_large_image(case2, rast, oracle):
     """The aux launches choose their instantiations by tile count as the plain ones do, so the
     large-image pair gets its own case: 20000 Gaussians at 1024x1024 (4096 tiles), SH1.
     The scene seed is chosen on the reference alone.  A (pixel, Gaussian) pair whose alpha lies within
@@ -135,13 +146,8 @@ def test_parity_large_image(rast, oracle):
     others come within 1.4e-7, 7.7e-8, 4.5e-7, 2.8e-7 and 1.5e-7).  Seed 4 was measured on the MI355X:
     its 1.4e-7 pair (pixel (753, 536), Gaussian 15674) flipped, in the colour pass as well, and put the
     opacity gradient at rel-L2 1.39e-4 (0.29 of the tensor's 2063 from that one Gaussian)."""
-    gr, sc = pkg("graphics"), pkg("scene")
-    cam = gr.synthetic_camera(1024, 1024)
-    assert cam.grid[0] * cam.grid[1] == 4096
-    s = sc.make_scene(cam, 20000, max_sh_degree=3, seed=5)
-    dC = sc.make_dL_dpix(cam, seed=6)
-    dD, dA = make_aux_grads(cam, seed=7)
-    _run(rast, oracle, cam, _scene_inputs(s), 1, dC, dD, dA, False)
+    cam, inputs, dC, dD, dA = case2
+    _run(rast, oracle, cam, inputs, 1, dC, dD, dA, False)
 
 
 def _chunk_tables(st, cam):
@@ -220,12 +226,13 @@ def test_precomputed_inputs(rast, oracle):
 
 
 # ---- case 6: colour untouched ----
-def test_colour_path_unchanged(case1, rast):
-    cam, s, inputs, dC, dD, dA = case1
+def _colour_path_unchanged(rast, cam, inputs, D, dC):
+    """forward_aux against forward, and backward_aux without aux gradients and the plain backward of
+    aux buffers against backward: bitwise equal (both sides are the library's own: no tolerance)."""
     native = pkg("native")
-    a = rast.forward(cam, **inputs, sh_degree=3)
+    a = rast.forward(cam, **inputs, sh_degree=D)
     for inverse in (False, True):
-        b = rast.forward_aux(cam, **inputs, sh_degree=3, inverse_depth=inverse)
+        b = rast.forward_aux(cam, **inputs, sh_degree=D, inverse_depth=inverse)
         assert torch.equal(a.color, b.color) and torch.equal(a.radii, b.radii)
         K = a.num_rendered
         assert b.num_rendered == K
@@ -238,10 +245,23 @@ def test_colour_path_unchanged(case1, rast):
         gc = rast.backward(b, dC)
         for k in ga:
             assert torch.equal(ga[k], gc[k]), k
+    return a
+
+
+def test_colour_path_unchanged(case1, rast):
+    cam, s, inputs, dC, dD, dA = case1
+    a = _colour_path_unchanged(rast, cam, inputs, 3, dC)
     with pytest.raises(RuntimeError, match="GSR_LAYOUT_AUX"):
         rast.backward_aux(a, dC, dD, dA)  # plain buffers hold no depth sums
     with pytest.raises(RuntimeError, match="full images only"):
         rast.forward_aux(cam, **inputs, sh_degree=3, tile_rows=(0, 4))
+
+
+def test_colour_path_unchanged_large_image(case2, rast):
+    """The other side of the blend launchers' tile-count selection, which the plain and the aux
+    launch share: 4096 tiles is the smallest image on the two-wave F6 and the plain-loop B1."""
+    cam, inputs, dC, dD, dA = case2
+    _colour_path_unchanged(rast, cam, inputs, 1, dC)
 
 
 # ---- case 7: edges ----
