@@ -2,6 +2,11 @@
 
   lib/libgsr_hip.so      hipcc --offload-arch=gfx950: the CDNA4 kernels + the C ABI
   lib/_gsr_torch*.so     libtorch render() + autograd Function (C++), links libgsr_hip.so
+  lib/gsr_dropin, gsr_train_loop, gsr_shard_step   C++ executables over the same libtorch layer
+
+The libtorch layer (csrc/torch/) is compiled once, position-independent, into lib/obj/*.o; the
+extension links those objects plus gsr_bind.cpp (the only pybind11 file), the executables link
+them plus gsr_trainer.cpp and their main.
 
 Per-file flags: gsr_preprocess.hip is compiled with -ffp-contract=off so its key-feeding
 arithmetic is bit-identical to the CPU oracle; the blend and preprocess-backward files too
@@ -118,29 +123,26 @@ def torch_ext_name() -> str:
 
 
 def build_torch_ext(verbose: bool = False, force: bool = False) -> str:
-    """Compile csrc/torch/gsr_torch.cpp against libtorch (host C++, no device code) and link
-    it to libgsr_hip.so with an $ORIGIN rpath, into lib/."""
+    """Link the libtorch layer's objects (host C++, no device code) and csrc/torch/gsr_bind.cpp,
+    the Python binding, to libgsr_hip.so with an $ORIGIN rpath, into lib/."""
     import torch
-    from torch.utils import cpp_extension
 
     os.makedirs(LIB, exist_ok=True)
     out = os.path.join(LIB, torch_ext_name())
-    srcs = [os.path.join(CSRC, "torch", f) for f in ("gsr_torch.cpp", "gsr_shard.cpp")]
-    tinc = cpp_extension.include_paths()
-    flags = ["-O2", "-std=c++17", "-fPIC", "-shared", "-D__HIP_PLATFORM_AMD__=1",
-             "-DTORCH_EXTENSION_NAME=_gsr_torch", "-DTORCH_API_INCLUDE_EXTENSION_H",
-             f"-D_GLIBCXX_USE_CXX11_ABI={int(torch._C._GLIBCXX_USE_CXX11_ABI)}",
-             "-I" + os.path.join(ROOT, "include"), "-I/opt/rocm/include",
-             "-I" + sysconfig.get_paths()["include"]] + ["-I" + p for p in tinc]
+    bind = os.path.join(CSRC, "torch", "gsr_bind.cpp")
+    cflags, _ = _exe_flags()
+    objs = _compile_exe_objs(cflags, force, LAYER_SOURCES)
+    flags = cflags + ["-shared", "-DTORCH_EXTENSION_NAME=_gsr_torch", "-DTORCH_API_INCLUDE_EXTENSION_H",
+                      "-I" + sysconfig.get_paths()["include"]]
     tlib = os.path.join(os.path.dirname(torch.__file__), "lib")
     libs = ["-L" + LIB, "-lgsr_hip", "-Wl,-rpath,$ORIGIN", "-L" + tlib, "-lc10", "-ltorch",
             "-ltorch_cpu", "-ltorch_python", "-lc10_hip", "-Wl,-rpath," + tlib]
-    stamp = _stamp(srcs + _headers() + EXE_HEADERS, " ".join(flags))
+    stamp = _stamp([bind] + LAYER_SOURCES + _headers() + EXE_HEADERS, " ".join(flags))
     stamp_file = out + ".stamp"
     if not force and os.path.exists(out) and os.path.exists(stamp_file) and open(stamp_file).read() == stamp:
         return out
     cxx = shutil.which("g++") or "c++"
-    cmd = [cxx] + flags + ["-I" + os.path.join(CSRC, "torch")] + srcs + ["-o", out] + libs
+    cmd = [cxx] + flags + [bind] + objs + ["-o", out] + libs
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(f"torch extension build failed:\n{' '.join(cmd)}\n{r.stdout}\n{r.stderr}")
@@ -189,7 +191,7 @@ def _exe_flags():
     from torch.utils import cpp_extension
 
     tlib = os.path.join(os.path.dirname(torch.__file__), "lib")
-    flags = ["-O2", "-std=c++17", "-DGSR_NO_PYBIND", "-D__HIP_PLATFORM_AMD__=1",
+    flags = ["-O2", "-std=c++17", "-fPIC", "-D__HIP_PLATFORM_AMD__=1",
              f"-D_GLIBCXX_USE_CXX11_ABI={int(torch._C._GLIBCXX_USE_CXX11_ABI)}",
              "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(CSRC, "torch"), "-I/opt/rocm/include"]
     flags += ["-I" + p for p in cpp_extension.include_paths()]
@@ -207,13 +209,19 @@ def _exe_flags():
     return flags, libs
 
 
-# the libtorch layer shared by the C++ executables (compiled once, -DGSR_NO_PYBIND)
-EXE_LIB_SOURCES = [os.path.join(CSRC, "torch", f) for f in ("gsr_torch.cpp", "gsr_trainer.cpp", "gsr_shard.cpp")]
-EXE_HEADERS = [os.path.join(CSRC, "torch", h) for h in ("gsr_render.h", "gsr_trainer.h", "gsr_shard.h")]
+# the libtorch layer: LAYER_SOURCES go into the extension and the C++ executables alike (compiled
+# once, -fPIC), the trainer into the executables only
+LAYER_SOURCES = [os.path.join(CSRC, "torch", f) for f in ("gsr_torch.cpp", "gsr_exchange.cpp", "gsr_plan.cpp",
+                                                          "gsr_shard.cpp")]
+EXE_LIB_SOURCES = LAYER_SOURCES + [os.path.join(CSRC, "torch", "gsr_trainer.cpp")]
+EXE_HEADERS = [os.path.join(CSRC, "torch", h) for h in ("gsr_render.h", "gsr_trainer.h", "gsr_shard.h",
+                                                        "gsr_exchange.h", "gsr_plan.h")]
 
 
-def _compile_exe_objs(flags, force: bool) -> list:
-    """gsr_torch.cpp + gsr_trainer.cpp -> lib/obj/*.o (content-stamped)."""
+def _compile_exe_objs(flags, force: bool, sources=None) -> list:
+    """Each of `sources` (default: EXE_LIB_SOURCES, the whole libtorch layer without its Python
+    binding) -> lib/obj/<name>.o, content-stamped per object: its source, the headers, the flags."""
+    sources = sources or EXE_LIB_SOURCES
     obj_dir = os.path.join(LIB, "obj")
     os.makedirs(obj_dir, exist_ok=True)
     cxx = shutil.which("g++") or "c++"
@@ -231,8 +239,8 @@ def _compile_exe_objs(flags, force: bool) -> list:
             fh.write(stamp)
         return obj
 
-    with cf.ThreadPoolExecutor(max_workers=len(EXE_LIB_SOURCES)) as ex:
-        return list(ex.map(one, EXE_LIB_SOURCES))
+    with cf.ThreadPoolExecutor(max_workers=len(sources)) as ex:
+        return list(ex.map(one, sources))
 
 
 def _build_exe(name: str, main_src: str, force: bool = False) -> str:

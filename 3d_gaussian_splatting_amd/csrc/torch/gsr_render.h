@@ -214,6 +214,30 @@ RenderOutput render(const RasterCamera& cam, Model& pc, const Pipe& pipe, const 
 }
 
 namespace detail {
+// ---- tensors -> C ABI structs, for the autograd Functions, gsr::Trainer and gsr::ShardStep ----
+// The tensor arguments of a rasterization, in the order of the autograd Functions' forward()
+// (means2D only receives a gradient).  An absent optional input is undefined or has 0 elements.
+struct Inputs {
+    torch::Tensor means3D, means2D, sh_dc, sh_rest, colors, opac, scales, rots, cov3D;
+};
+bool present(const torch::Tensor& t);
+// gsr_gaussians over rows [g0, g1) of the inputs (g1 < 0: all of them); every present input is
+// checked to be a contiguous f32 device tensor of P rows.  With colors given, the SH inputs and
+// the degree are left out (F1, B2 and the ABI's validation ignore them then).
+gsr_gaussians make_gaussians(const Inputs& in, int sh_degree, float scale_modifier, int64_t g0 = 0, int64_t g1 = -1);
+gsr_raster_settings make_settings(const RasterSettings& rs);
+// The leaf gradient tensors of one backward over `rows` Gaussians, in the canonical shapes
+// (rows,3) means2D / conic / means3D / colors / scales, (rows,1) opac, (rows,1,3) dc,
+// (rows,M,3) rest, (rows,4) rots, (rows,6) cov, and the gsr_grads pointing at them.  Which of
+// colors | dc, rest and cov | scales, rots exist follows the inputs; conic (B2's dL_dconic
+// output) only on request.
+struct LeafGrads {
+    torch::Tensor means2D, conic, opac, means3D, dc, rest, colors, scales, rots, cov;
+    gsr_grads gg{};
+    LeafGrads() = default;
+    LeafGrads(const Inputs& in, int64_t rows, bool want_conic);
+};
+
 // The forward / backward of RasterizeGaussians without autograd (the native trainer's path,
 // gsr_trainer.h): torch owns every scratch byte; `Frame` keeps them from forward to backward.
 struct Frame {
@@ -224,15 +248,10 @@ struct Frame {
     gsr_raster_settings settings{};
     torch::Tensor k_device() const;  // (1,) int32 device copy of the scan's K
 };
-Frame forward(const RasterCamera& cam, const RasterSettings& rs, const torch::Tensor& means3D,
-              const torch::Tensor& sh_dc, const torch::Tensor& sh_rest, const torch::Tensor& colors,
-              const torch::Tensor& opac, const torch::Tensor& scales, const torch::Tensor& rots,
-              const torch::Tensor& cov3D);
-// gsr_backward into the given gradient tensors (undefined = not requested where nullable)
-void backward(const Frame& f, const RasterSettings& rs, const torch::Tensor& means3D, const torch::Tensor& sh_dc,
-              const torch::Tensor& sh_rest, const torch::Tensor& colors, const torch::Tensor& opac,
-              const torch::Tensor& scales, const torch::Tensor& rots, const torch::Tensor& cov3D,
-              const torch::Tensor& dL_dcolor, const gsr_grads& grads);
+Frame forward(const RasterCamera& cam, const RasterSettings& rs, const Inputs& in);
+// gsr_backward of that frame into the given gradient outputs
+void backward(const Frame& f, const RasterSettings& rs, const Inputs& in, const torch::Tensor& dL_dcolor,
+              const gsr_grads& grads);
 void check(int rc, const char* what);
 void* current_stream();
 }  // namespace detail

@@ -7,11 +7,11 @@
 //   gsr_shard_forward -> all-to-all of the splat blocks -> gsr_band_forward
 //   -> all-gather of the band images (on a second stream, overlapping B1)
 //   -> gsr_band_backward -> all-to-all of the 2D-gradient rows back -> gsr_shard_backward.
-// The collectives go through an `Exchange`: RCCL over xGMI (grouped ncclSend / ncclRecv for the
-// all-to-alls, ncclAllGather for the bands) on the GPU box, or a host-staged exchange through a
-// c10d::Store for ranks that share one GPU (the two-process test; RCCL refuses two ranks on one
-// device).  The step is sync-free (fixed capacities from plan(); K stays on the device), so with
-// an RCCL exchange it is captured once into a hipGraph and replayed: one graph launch per step.
+// The collectives go through an `Exchange` (gsr_exchange.h): RCCL on the GPU box, a host-staged
+// store exchange or an in-process group for ranks that share one GPU; the cuts and capacities come
+// from the partition arithmetic of gsr_plan.h.  The step is sync-free (fixed capacities from
+// plan(); K stays on the device), so with an RCCL exchange it is captured once into a hipGraph
+// and replayed: one graph launch per step.
 //
 // Overflow agreement: each rank's send-header counts and band K ride in a status footer of its
 // band image, so the all-gather hands every rank the status of ALL ranks; the gathered footers
@@ -20,7 +20,6 @@
 // raises ShardOverflowError together -- no rank is left blocked in a collective its peers no
 // longer join.
 #pragma once
-#include <hip/hip_runtime.h>  // hipStream_t only: the step itself uses libtorch streams / graphs
 #include <torch/torch.h>
 
 #include <array>
@@ -32,75 +31,16 @@
 #include <vector>
 
 #include "gsr/gsr.h"
+#include "gsr_exchange.h"
+#include "gsr_plan.h"
 #include "gsr_render.h"
-
-namespace c10d {
-class Store;
-}
 
 namespace gsr {
 
-// ---- transport -----------------------------------------------------------------------------
-class Exchange {
-   public:
-    virtual ~Exchange() = default;
-    virtual int rank() const = 0;
-    virtual int world() const = 0;
-    virtual bool capturable() const = 0;  // may be recorded into a hipGraph
-    virtual const char* name() const = 0;
-    // the transport's own count of ranks (RCCL: ncclCommCount), for reports
-    virtual int comm_world() const { return world(); }
-    // block b of `send` (block_bytes each) -> rank b; block s of `recv` <- rank s
-    virtual void all_to_all(const void* send, void* recv, size_t block_bytes, hipStream_t s) = 0;
-    // `bytes` from every rank into recv, rank-major
-    virtual void all_gather(const void* send, void* recv, size_t bytes, hipStream_t s) = 0;
-    // in place over ranks (setup only)
-    virtual void all_reduce_i64(int64_t* buf, size_t n, bool max, hipStream_t s) = 0;
-};
-
-// RCCL: rank 0 makes the unique id, the caller broadcasts it (torch.distributed, a store, ...).
-std::vector<uint8_t> rccl_unique_id();
-std::unique_ptr<Exchange> rccl_exchange(const std::vector<uint8_t>& unique_id, int rank, int world);
-// RCCL with the id passed through a c10d::Store (key "gsr/rccl_id").
-std::unique_ptr<Exchange> rccl_exchange(c10d::Store& store, int rank, int world);
-// Host-staged through a c10d::Store (device -> host -> store -> host -> device); not capturable.
-std::unique_ptr<Exchange> store_exchange(std::shared_ptr<c10d::Store> store, int rank, int world);
-
-// In-process rank group (one-GPU rehearsal of the N-rank step, scripts/band_sim.py --cpp): every
-// rank's ShardStep runs in its own host thread on the same device, and the collectives are
-// device-to-device copies between the ranks' own buffers, ordered by events and host barriers.
-// After a live step each exchange keeps what it delivered (recv blocks, gathered rows, gradient
-// blocks); in replay mode it copies those instead of waiting for peers, so ONE rank's whole C++
-// step (glue, graph replay and exchange-sized copies included) can be timed alone on the GPU.
-class LocalGroup;
-std::shared_ptr<LocalGroup> local_group(int world);
-std::unique_ptr<Exchange> local_exchange(std::shared_ptr<LocalGroup> group, int rank);
-// replay: copy the last live step's deliveries (copies) or move nothing (the receive buffers
-// still hold them); throws unless ex is a local exchange
-void local_exchange_set_replay(Exchange& ex, bool on, bool copies = true);
 class ShardStep;
 // steps[r].plan() / steps[r].step(dpix) x n in one host thread per rank (exceptions rethrown)
 void run_ranks_plan(const std::vector<ShardStep*>& steps);
 void run_ranks_steps(const std::vector<ShardStep*>& steps, const torch::Tensor& dpix, int n);
-
-// ---- partition (bands.py) -------------------------------------------------------------------
-std::pair<int64_t, int64_t> gaussian_shard(int64_t P, int world, int rank);
-std::vector<int> equal_bands(int grid_y, int world);
-std::vector<int> balance_bands(const std::vector<int64_t>& row_counts, int world);
-
-// Band cuts and capacities from one step's statistics (GSR_FLAG_ROW_SPANS of every shard, summed
-// or per shard): inst[y] = instances in tile row y over all shards; starts[s][y] / ends[s][y] =
-// shard s's visible Gaussians whose rect's first / last tile row is y.  The splats shard s sends
-// to band [r0, r1) are exactly sum_{y<r1} starts[s][y] - sum_{y<r0} ends[s][y], so the needed
-// pair_cap and band capacity (before headroom) follow for any cuts.  Same arithmetic as
-// bands.plan_from_stats.
-struct StatsPlan {
-    std::vector<int> rows;
-    int64_t max_splats = 0;  // largest (shard, band) splat count under `rows`
-    std::vector<int64_t> band_k;
-};
-StatsPlan plan_from_stats(const std::vector<int64_t>& inst, const std::vector<std::vector<int64_t>>& starts,
-                          const std::vector<std::vector<int64_t>>& ends, int world);
 
 class ShardOverflowError : public std::overflow_error {
    public:
@@ -120,6 +60,9 @@ struct ShardInputs {
     torch::Tensor means3D, opacities, scales, rotations, sh_dc, sh_rest, colors_precomp, cov3D_precomp;
     int sh_degree = 0;
     float scale_modifier = 1.f;
+    detail::Inputs inputs() const {  // as the shared glue's argument list (gsr_render.h)
+        return {means3D, {}, sh_dc, sh_rest, colors_precomp, opacities, scales, rotations, cov3D_precomp};
+    }
 };
 
 class ShardStep {
@@ -199,8 +142,9 @@ class ShardStep {
     void push_status();
     void poll(bool wait_all);
     void replan_live();
-    gsr_gaussians shard_struct() const;
-    gsr_raster_settings shard_settings() const;
+    gsr_gaussians shard_gaussians() const {
+        return detail::make_gaussians(in_, rs_.sh_degree, rs_.scale_modifier, g0_, g1_);
+    }
     gsr_raster_settings band_settings() const;
     void size_buffers();
     void drop_graph();
@@ -208,8 +152,8 @@ class ShardStep {
     Exchange& ex_;
     RasterCamera cam_;
     gsr_camera ccam_;
-    ShardInputs in_;
-    std::array<float, 3> bg_;
+    detail::Inputs in_;
+    RasterSettings rs_;  // bg, SH degree, scale modifier; the whole image, no bound
     double headroom_;
     bool graph_;
     int lag_;

@@ -1,6 +1,7 @@
-// gsr_torch.cpp -- libtorch layer over the C ABI: RasterizeGaussians autograd Function,
-// render() helpers and the Python binding (_gsr_torch).  Host C++ only: every byte of device
-// work goes through include/gsr/gsr.h into libgsr_hip.so (no torch types cross that ABI).
+// gsr_torch.cpp -- libtorch layer over the C ABI: the tensor-to-ABI glue (gsr_render.h detail::),
+// the RasterizeGaussians autograd Functions and the render() helpers.  Host C++ only: every byte
+// of device work goes through include/gsr/gsr.h into libgsr_hip.so (no torch types cross that
+// ABI).  The Python binding of this layer is gsr_bind.cpp.
 //
 // Scratch buffers (geometry / binning / image) are uint8 tensors from torch's caching
 // allocator, created inside the C ABI's allocation callbacks and kept in the autograd context
@@ -8,11 +9,7 @@
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 #include <c10/core/Event.h>
 #include <c10/hip/HIPStream.h>
-#ifdef GSR_NO_PYBIND
 #include <torch/torch.h>
-#else
-#include <torch/extension.h>
-#endif
 
 #include <cmath>
 #include <cstdio>
@@ -27,67 +24,45 @@ void check(int rc, const char* what) {
                                           gsr_last_error());
 }
 void* current_stream() { return (void*)c10::hip::getCurrentHIPStream().stream(); }
-}  // namespace detail
-
-namespace {
-using detail::check;
-
-struct AllocCtx {
-    torch::Device device;
-    std::vector<torch::Tensor> keep;
-};
-
-void* alloc_cb(void* ctx, size_t bytes) {
-    auto* c = static_cast<AllocCtx*>(ctx);
-    auto t = torch::empty({(int64_t)std::max<size_t>(bytes, 16)},
-                          torch::TensorOptions().dtype(torch::kUInt8).device(c->device));
-    c->keep.push_back(t);
-    return t.data_ptr();
-}
 
 // absent optional inputs travel through autograd as defined 0-element tensors (undefined
 // tensors are rejected by Function::apply's input bookkeeping)
 bool present(const torch::Tensor& t) { return t.defined() && t.numel() > 0; }
 
-const float* fptr(const torch::Tensor& t, const char* name, int64_t P, int64_t per) {
-    if (!present(t)) return nullptr;
-    TORCH_CHECK(t.is_cuda(), name, " must be a GPU tensor");
-    TORCH_CHECK(t.scalar_type() == torch::kFloat32, name, " must be float32");
-    TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
-    TORCH_CHECK(t.numel() == P * per, name, " has ", t.numel(), " elements, expected ", P * per);
-    return t.data_ptr<float>();
-}
-
-// the tensor arguments of a rasterization, in the order of the autograd Functions' forward()
-// (means2D only receives a gradient)
-struct Inputs {
-    torch::Tensor means3D, means2D, sh_dc, sh_rest, colors, opac, scales, rots, cov3D;
-};
-
-gsr_gaussians make_gaussians(const RasterSettings& rs, const Inputs& in) {
+gsr_gaussians make_gaussians(const Inputs& in, int sh_degree, float scale_modifier, int64_t g0, int64_t g1) {
     gsr_gaussians g{};
     const int64_t P = in.means3D.size(0);
-    g.P = (int32_t)P;
-    g.sh_degree = rs.sh_degree;
-    g.scale_modifier = rs.scale_modifier;
-    g.means3D = fptr(in.means3D, "means3D", P, 3);
-    g.opacities = fptr(in.opac, "opacities", P, 1);
+    if (g1 < 0) g1 = P;
+    TORCH_CHECK(0 <= g0 && g0 <= g1 && g1 <= P, "rows [", g0, ", ", g1, ") outside the ", P, " Gaussians");
+    auto rows = [&](const torch::Tensor& t, const char* name, int64_t per) -> const float* {
+        if (!present(t)) return nullptr;
+        TORCH_CHECK(t.is_cuda(), name, " must be a GPU tensor");
+        TORCH_CHECK(t.scalar_type() == torch::kFloat32, name, " must be float32");
+        TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+        TORCH_CHECK(t.numel() == P * per, name, " has ", t.numel(), " elements, expected ", P * per);
+        return t.data_ptr<float>() + g0 * per;
+    };
+    g.P = (int32_t)(g1 - g0);
+    g.sh_degree = sh_degree;
+    g.scale_modifier = scale_modifier;
+    g.means3D = rows(in.means3D, "means3D", 3);
+    g.opacities = rows(in.opac, "opacities", 1);
     if (present(in.colors)) {
-        g.colors_precomp = fptr(in.colors, "colors_precomp", P, 3);
+        g.colors_precomp = rows(in.colors, "colors_precomp", 3);
         g.sh_degree = 0;
     } else {
-        g.sh_dc = fptr(in.sh_dc, "sh_dc", P, 3);
+        g.sh_dc = rows(in.sh_dc, "sh_dc", 3);
         if (present(in.sh_rest)) {
             const int64_t M = in.sh_rest.numel() / std::max<int64_t>(P, 1) / 3;
-            g.sh_rest = fptr(in.sh_rest, "sh_rest", P, 3 * M);
+            g.sh_rest = rows(in.sh_rest, "sh_rest", 3 * M);
             g.sh_rest_coeffs = (int32_t)M;
         }
     }
     if (present(in.cov3D)) {
-        g.cov3D_precomp = fptr(in.cov3D, "cov3D_precomp", P, 6);
+        g.cov3D_precomp = rows(in.cov3D, "cov3D_precomp", 6);
     } else {
-        g.scales = fptr(in.scales, "scales", P, 3);
-        g.rotations = fptr(in.rots, "rotations", P, 4);
+        g.scales = rows(in.scales, "scales", 3);
+        g.rotations = rows(in.rots, "rotations", 4);
     }
     return g;
 }
@@ -102,22 +77,60 @@ gsr_raster_settings make_settings(const RasterSettings& rs) {
     return s;
 }
 
-void* cur_stream() { return detail::current_stream(); }
+LeafGrads::LeafGrads(const Inputs& in, int64_t rows, bool want_conic) {
+    const auto fo = in.means3D.options();
+    auto out = [&](torch::Tensor& t, std::initializer_list<int64_t> shape) {
+        t = torch::empty(shape, fo);
+        return t.data_ptr<float>();
+    };
+    gg.dL_dmeans2D = out(means2D, {rows, 3});
+    if (want_conic) gg.dL_dconic = out(conic, {rows, 3});
+    gg.dL_dopacity = out(opac, {rows, 1});
+    gg.dL_dmeans3D = out(means3D, {rows, 3});
+    if (present(in.colors)) {
+        gg.dL_dcolors = out(colors, {rows, 3});
+    } else {
+        gg.dL_dsh_dc = out(dc, {rows, 1, 3});
+        if (present(in.sh_rest))
+            gg.dL_dsh_rest = out(rest, {rows, in.sh_rest.numel() / std::max<int64_t>(in.means3D.size(0), 1) / 3, 3});
+    }
+    if (present(in.cov3D)) {
+        gg.dL_dcov3D = out(cov, {rows, 6});
+    } else {
+        gg.dL_dscales = out(scales, {rows, 3});
+        gg.dL_drotations = out(rots, {rows, 4});
+    }
+}
+}  // namespace detail
 
-using FwdResult = detail::Frame;
+namespace {
+using namespace detail;  // check, Inputs, make_gaussians, make_settings, LeafGrads, present
 
-FwdResult forward_impl(const RasterCamera& cam, const RasterSettings& rs, const Inputs& in, bool aux = false,
+struct AllocCtx {
+    torch::Device device;
+    std::vector<torch::Tensor> keep;
+};
+
+void* alloc_cb(void* ctx, size_t bytes) {
+    auto* c = static_cast<AllocCtx*>(ctx);
+    auto t = torch::empty({(int64_t)std::max<size_t>(bytes, 16)},
+                          torch::TensorOptions().dtype(torch::kUInt8).device(c->device));
+    c->keep.push_back(t);
+    return t.data_ptr();
+}
+
+Frame forward_impl(const RasterCamera& cam, const RasterSettings& rs, const Inputs& in, bool aux = false,
                        bool inverse_depth = false) {
     const torch::Tensor& means3D = in.means3D;
     TORCH_CHECK(means3D.dim() == 2 && means3D.size(1) == 3, "means3D must be (P,3)");
     const int64_t P = means3D.size(0);
     auto dev = means3D.device();
     auto fopt = torch::TensorOptions().dtype(torch::kFloat32).device(dev);
-    FwdResult r;
+    Frame r;
     r.color = torch::empty({3, cam.height, cam.width}, fopt);
     r.radii = torch::empty({P}, fopt.dtype(torch::kInt32));
     const gsr_camera c = cam.to_c();
-    const gsr_gaussians g = make_gaussians(rs, in);
+    const gsr_gaussians g = make_gaussians(in, rs.sh_degree, rs.scale_modifier);
     gsr_raster_settings s = make_settings(rs);
     AllocCtx geom{dev, {}}, bin{dev, {}}, img{dev, {}};
     gsr_buffers b{};
@@ -131,11 +144,11 @@ FwdResult forward_impl(const RasterCamera& cam, const RasterSettings& rs, const 
         r.alpha = torch::empty({cam.height, cam.width}, fopt);
         s.flags |= GSR_FLAG_AUX | (inverse_depth ? GSR_FLAG_INVDEPTH : 0u);
         const gsr_aux_out ao{r.depth.data_ptr<float>(), r.alpha.data_ptr<float>()};
-        check(gsr_forward_aux(&c, &g, &s, r.color.data_ptr<float>(), rad, a0, a1, a2, (void*)ctxs, &b, cur_stream(),
+        check(gsr_forward_aux(&c, &g, &s, r.color.data_ptr<float>(), rad, a0, a1, a2, (void*)ctxs, &b, current_stream(),
                               &ao),
               "gsr_forward_aux");
     } else {
-        check(gsr_forward(&c, &g, &s, r.color.data_ptr<float>(), rad, a0, a1, a2, (void*)ctxs, &b, cur_stream()),
+        check(gsr_forward(&c, &g, &s, r.color.data_ptr<float>(), rad, a0, a1, a2, (void*)ctxs, &b, current_stream()),
               "gsr_forward");
     }
     r.geom = geom.keep.at(0);
@@ -173,7 +186,7 @@ struct SavedFrame {
     bool has_m2d;
 };
 
-void save_frame(AutogradContext* ctx, const RasterCamera& cam, const RasterSettings& rs, const FwdResult& r,
+void save_frame(AutogradContext* ctx, const RasterCamera& cam, const RasterSettings& rs, const Frame& r,
                 const torch::Tensor& means2D) {
     auto doubles = [](const auto& a) { return std::vector<double>(a.begin(), a.end()); };
     // restore_frame reads the integers and the scalars back by position
@@ -208,42 +221,6 @@ SavedFrame restore_frame(AutogradContext* ctx) {
     return f;
 }
 
-// The leaf gradient tensors of one backward and the gsr_grads pointing at them.
-struct LeafGrads {
-    torch::Tensor means2D, opac, means3D, dc, rest, colors, scales, rots, cov;
-    gsr_grads gg{};
-    explicit LeafGrads(const Inputs& in) {
-        const int64_t P = in.means3D.size(0);
-        auto fo = in.means3D.options();
-        means2D = torch::empty({P, 3}, fo);
-        opac = torch::empty_like(in.opac);
-        means3D = torch::empty({P, 3}, fo);
-        gg.dL_dmeans2D = means2D.data_ptr<float>();
-        gg.dL_dopacity = opac.data_ptr<float>();
-        gg.dL_dmeans3D = means3D.data_ptr<float>();
-        if (present(in.colors)) {
-            colors = torch::empty_like(in.colors);
-            gg.dL_dcolors = colors.data_ptr<float>();
-        } else {
-            dc = torch::empty_like(in.sh_dc);
-            gg.dL_dsh_dc = dc.data_ptr<float>();
-            if (present(in.sh_rest)) {
-                rest = torch::empty_like(in.sh_rest);
-                gg.dL_dsh_rest = rest.data_ptr<float>();
-            }
-        }
-        if (present(in.cov3D)) {
-            cov = torch::empty_like(in.cov3D);
-            gg.dL_dcov3D = cov.data_ptr<float>();
-        } else {
-            scales = torch::empty_like(in.scales);
-            rots = torch::empty_like(in.rots);
-            gg.dL_dscales = scales.data_ptr<float>();
-            gg.dL_drotations = rots.data_ptr<float>();
-        }
-    }
-};
-
 // forward() of both autograd Functions: the render (inverse_depth != nullptr: with the depth and
 // alpha channels), everything backward needs, and the outputs {color, (depth, alpha,) radii, K on
 // the device, (K, capacity)}, all but the images non-differentiable.
@@ -272,9 +249,9 @@ variable_list backward_saved(AutogradContext* ctx, const variable_list& grad_out
     const SavedFrame f = restore_frame(ctx);
     auto dL_dcolor = aux && !grad_out[0].defined() ? torch::zeros({3, f.cam.height, f.cam.width}, in.means3D.options())
                                                    : grad_out[0].contiguous();
-    LeafGrads lg(in);
+    const LeafGrads lg(in, in.means3D.size(0), /*want_conic=*/false);
     const gsr_camera c = f.cam.to_c();
-    const gsr_gaussians g = make_gaussians(f.rs, in);
+    const gsr_gaussians g = make_gaussians(in, f.rs.sh_degree, f.rs.scale_modifier);
     gsr_raster_settings s = make_settings(f.rs);
     const gsr_buffers b = buffers_of(sv[8], sv[9], sv[10], f.K, f.cap, f.n_local, f.layout);
     AllocCtx scratch{in.means3D.device(), {}};
@@ -285,15 +262,18 @@ variable_list backward_saved(AutogradContext* ctx, const variable_list& grad_out
         s.flags |= GSR_FLAG_AUX | (ctx->saved_data["inverse_depth"].toBool() ? GSR_FLAG_INVDEPTH : 0u);
         const gsr_aux_grads ag{dL_ddepth.defined() ? dL_ddepth.data_ptr<float>() : nullptr,
                                dL_dalpha.defined() ? dL_dalpha.data_ptr<float>() : nullptr};
-        check(gsr_backward_aux(&c, &g, &s, &b, dL_dcolor.data_ptr<float>(), alloc_cb, &scratch, &lg.gg, cur_stream(),
+        check(gsr_backward_aux(&c, &g, &s, &b, dL_dcolor.data_ptr<float>(), alloc_cb, &scratch, &lg.gg, current_stream(),
                                &ag),
               "gsr_backward_aux");
     } else {
-        check(gsr_backward(&c, &g, &s, &b, dL_dcolor.data_ptr<float>(), alloc_cb, &scratch, &lg.gg, cur_stream()),
+        check(gsr_backward(&c, &g, &s, &b, dL_dcolor.data_ptr<float>(), alloc_cb, &scratch, &lg.gg, current_stream()),
               "gsr_backward");
     }
-    if (!f.has_m2d) lg.means2D = torch::Tensor();
-    return {lg.means3D, lg.means2D, lg.dc, lg.rest, lg.colors, lg.opac, lg.scales, lg.rots, lg.cov};
+    // the canonical shapes, viewed as each input's own
+    auto like = [](const torch::Tensor& g, const torch::Tensor& x) { return g.defined() ? g.view(x.sizes()) : g; };
+    return {lg.means3D, f.has_m2d ? lg.means2D : torch::Tensor(), like(lg.dc, in.sh_dc), like(lg.rest, in.sh_rest),
+            like(lg.colors, in.colors), like(lg.opac, in.opac), like(lg.scales, in.scales), like(lg.rots, in.rots),
+            like(lg.cov, in.cov3D)};
 }
 
 class RasterizeGaussians : public torch::autograd::Function<RasterizeGaussians> {
@@ -357,23 +337,18 @@ torch::Tensor Frame::k_device() const {
     return image.narrow(0, off, 4).view(torch::kInt32).clone();  // async device copy
 }
 
-Frame forward(const RasterCamera& cam, const RasterSettings& rs, const torch::Tensor& means3D,
-              const torch::Tensor& sh_dc, const torch::Tensor& sh_rest, const torch::Tensor& colors,
-              const torch::Tensor& opac, const torch::Tensor& scales, const torch::Tensor& rots,
-              const torch::Tensor& cov3D) {
-    return forward_impl(cam, rs, {means3D, {}, sh_dc, sh_rest, colors, opac, scales, rots, cov3D});
+Frame forward(const RasterCamera& cam, const RasterSettings& rs, const Inputs& in) {
+    return forward_impl(cam, rs, in);
 }
 
-void backward(const Frame& f, const RasterSettings& rs, const torch::Tensor& means3D, const torch::Tensor& sh_dc,
-              const torch::Tensor& sh_rest, const torch::Tensor& colors, const torch::Tensor& opac,
-              const torch::Tensor& scales, const torch::Tensor& rots, const torch::Tensor& cov3D,
-              const torch::Tensor& dL_dcolor, const gsr_grads& grads) {
-    const gsr_gaussians g = make_gaussians(rs, {means3D, {}, sh_dc, sh_rest, colors, opac, scales, rots, cov3D});
+void backward(const Frame& f, const RasterSettings& rs, const Inputs& in, const torch::Tensor& dL_dcolor,
+              const gsr_grads& grads) {
+    const gsr_gaussians g = make_gaussians(in, rs.sh_degree, rs.scale_modifier);
     TORCH_CHECK(dL_dcolor.is_contiguous() && dL_dcolor.numel() == 3LL * f.cam.width * f.cam.height,
                 "dL_dcolor must be a contiguous (3,H,W) tensor");
-    AllocCtx scratch{means3D.device(), {}};
+    AllocCtx scratch{in.means3D.device(), {}};
     check(gsr_backward(&f.cam, &g, &f.settings, &f.bufs, dL_dcolor.data_ptr<float>(), alloc_cb, &scratch, &grads,
-                       cur_stream()),
+                       current_stream()),
           "gsr_backward");
 }
 }  // namespace detail
@@ -547,95 +522,3 @@ torch::Tensor eval_sh_colors(int D, const torch::Tensor& sh, const torch::Tensor
 }
 
 }  // namespace gsr
-
-// ------------------------------------------------------------------------------------------
-// Python binding (compile with -DGSR_NO_PYBIND when linking into a C++ executable)
-// ------------------------------------------------------------------------------------------
-#ifndef GSR_NO_PYBIND
-namespace py = pybind11;
-
-static gsr::RasterCamera cam_from_py(int w, int h, float tx, float ty, const std::vector<float>& v,
-                                     const std::vector<float>& p, const std::vector<float>& c) {
-    TORCH_CHECK(v.size() == 16 && p.size() == 16 && c.size() == 3, "bad camera arrays");
-    gsr::RasterCamera cam;
-    cam.width = w;
-    cam.height = h;
-    cam.tanfovx = tx;
-    cam.tanfovy = ty;
-    for (int i = 0; i < 16; ++i) cam.viewmatrix[i] = v[i], cam.projmatrix[i] = p[i];
-    for (int i = 0; i < 3; ++i) cam.campos[i] = c[i];
-    return cam;
-}
-
-static gsr::RasterSettings settings_from_py(const std::vector<float>& bg, float smod, int D, int ty0, int ty1,
-                                            bool debug, int max_rendered) {
-    gsr::RasterSettings rs;
-    rs.max_rendered = max_rendered;
-    for (int i = 0; i < 3; ++i) rs.bg[i] = bg.at(i);
-    rs.scale_modifier = smod;
-    rs.sh_degree = D;
-    rs.tile_y0 = ty0;
-    rs.tile_y1 = ty1;
-    rs.debug = debug;
-    return rs;
-}
-
-using OptTensor = c10::optional<torch::Tensor>;
-static torch::Tensor opt(const OptTensor& t) { return t.has_value() ? *t : torch::Tensor(); }
-
-namespace gsr {
-void bind_shard(pybind11::module& m);  // gsr_shard.cpp
-}
-
-PYBIND11_MODULE(_gsr_torch, m) {
-    m.doc() = "libtorch RasterizeGaussians over the gsr C ABI (libgsr_hip.so)";
-    py::class_<gsr::RasterCamera>(m, "RasterCamera")
-        .def(py::init(&cam_from_py), py::arg("width"), py::arg("height"), py::arg("tanfovx"),
-             py::arg("tanfovy"), py::arg("viewmatrix"), py::arg("projmatrix"), py::arg("campos"))
-        .def_readonly("width", &gsr::RasterCamera::width)
-        .def_readonly("height", &gsr::RasterCamera::height)
-        .def_readonly("tanfovx", &gsr::RasterCamera::tanfovx)
-        .def_readonly("tanfovy", &gsr::RasterCamera::tanfovy)
-        .def_readonly("viewmatrix", &gsr::RasterCamera::viewmatrix)
-        .def_readonly("projmatrix", &gsr::RasterCamera::projmatrix)
-        .def_readonly("campos", &gsr::RasterCamera::campos);
-    py::class_<gsr::RasterSettings>(m, "RasterSettings")
-        .def(py::init(&settings_from_py), py::arg("bg"), py::arg("scale_modifier") = 1.0f,
-             py::arg("sh_degree") = 0, py::arg("tile_y0") = 0, py::arg("tile_y1") = INT32_MAX,
-             py::arg("debug") = false, py::arg("max_rendered") = 0);
-    m.def(
-        "rasterize_gaussians",
-        [](const gsr::RasterCamera& cam, const gsr::RasterSettings& rs, torch::Tensor means3D, torch::Tensor means2D,
-           OptTensor sh_dc, OptTensor sh_rest, OptTensor colors, torch::Tensor opac, OptTensor scales, OptTensor rots,
-           OptTensor cov3D) {
-            auto r = gsr::rasterize(cam, rs, nullptr, {means3D, means2D, opt(sh_dc), opt(sh_rest), opt(colors), opac,
-                                                       opt(scales), opt(rots), opt(cov3D)});
-            return py::make_tuple(r[0], r[1]);
-        },
-        py::arg("cam"), py::arg("settings"), py::arg("means3D"), py::arg("means2D"), py::arg("sh_dc"),
-        py::arg("sh_rest"), py::arg("colors_precomp"), py::arg("opacities"), py::arg("scales"),
-        py::arg("rotations"), py::arg("cov3D_precomp"));
-    m.def(
-        "rasterize_gaussians_aux",
-        [](const gsr::RasterCamera& cam, const gsr::RasterSettings& rs, bool inverse_depth, torch::Tensor means3D,
-           torch::Tensor means2D, OptTensor sh_dc, OptTensor sh_rest, OptTensor colors, torch::Tensor opac,
-           OptTensor scales, OptTensor rots, OptTensor cov3D) {
-            auto r = gsr::rasterize(cam, rs, &inverse_depth, {means3D, means2D, opt(sh_dc), opt(sh_rest), opt(colors),
-                                                              opac, opt(scales), opt(rots), opt(cov3D)});
-            return py::make_tuple(r[0], r[1], r[2], r[3]);
-        },
-        py::arg("cam"), py::arg("settings"), py::arg("inverse_depth"), py::arg("means3D"), py::arg("means2D"),
-        py::arg("sh_dc"), py::arg("sh_rest"), py::arg("colors_precomp"), py::arg("opacities"), py::arg("scales"),
-        py::arg("rotations"), py::arg("cov3D_precomp"));
-    m.def("eval_sh_colors", &gsr::eval_sh_colors);
-    m.def(
-        "camera_from_tensors",
-        [](int w, int h, double fovx, double fovy, torch::Tensor wv, torch::Tensor fp, torch::Tensor cc) {
-            return gsr::RasterCamera::from_tensors(w, h, fovx, fovy, wv, fp, cc);
-        },
-        py::arg("width"), py::arg("height"), py::arg("FoVx"), py::arg("FoVy"), py::arg("world_view_transform"),
-        py::arg("full_proj_transform"), py::arg("camera_center"));
-    m.def("abi_version", []() { return gsr_abi_version(); });
-    gsr::bind_shard(m);
-}
-#endif  // GSR_NO_PYBIND

@@ -325,24 +325,20 @@ void Trainer::oneup_SH_degree() {
     if (active_sh_degree_ < max_sh_degree_) ++active_sh_degree_;
 }
 
-detail::Frame Trainer::render(const RasterCamera& cam, const std::array<float, 3>& bg, torch::Tensor& s,
-                              torch::Tensor& q, torch::Tensor& o) {
+detail::Frame Trainer::render(const RasterCamera& cam, RasterSettings& rs, detail::Inputs& in) {
     const int64_t P = num_points();
-    s = torch::empty_like(params_["scaling"]);
-    q = torch::empty_like(params_["rotation"]);
-    o = torch::empty_like(params_["opacity"]);
+    auto s = torch::empty_like(params_["scaling"]);
+    auto q = torch::empty_like(params_["rotation"]);
+    auto o = torch::empty_like(params_["opacity"]);
     check(gsr_activate(fp(params_["scaling"]), fp(params_["rotation"]), fp(params_["opacity"]), (int32_t)P, fp(s),
                        fp(q), fp(o), stream()),
           "gsr_activate");
-    RasterSettings rs;
-    rs.bg = bg;
     rs.sh_degree = active_sh_degree_;
     const int bound = binning_.bound();
     rs.max_rendered = bound;
-    o = o.reshape({-1});
     const auto& rest = params_["f_rest"];
-    auto f = detail::forward(cam, rs, params_["xyz"], params_["f_dc"], rest.size(1) ? rest : torch::Tensor(),
-                             torch::Tensor(), o, s, q, torch::Tensor());
+    in = {params_["xyz"], {}, params_["f_dc"], rest.size(1) ? rest : torch::Tensor(), {}, o.reshape({-1}), s, q, {}};
+    auto f = detail::forward(cam, rs, in);
     guard_k_ = bound > 0 ? f.k_device() : torch::Tensor();
     guard_cap_ = bound;
     binning_.observe(f.k_device(), f.bufs.num_rendered);
@@ -353,8 +349,10 @@ Trainer::StepResult Trainer::step(int iteration, const RasterCamera& cam, const 
                                   const std::array<float, 3>& bg, bool densify) {
     update_learning_rate(iteration);
     if (iteration % 1000 == 0) oneup_SH_degree();
-    torch::Tensor s, q, o;
-    detail::Frame fr = render(cam, bg, s, q, o);
+    RasterSettings rs;
+    rs.bg = bg;
+    detail::Inputs in;  // the activated values, built once for the forward and the backward
+    detail::Frame fr = render(cam, rs, in);
     const int64_t P = num_points();
     // loss forward / backward (gsr_train.h)
     const int C = 3, H = cam.height, W = cam.width;
@@ -368,32 +366,14 @@ Trainer::StepResult Trainer::step(int iteration, const RasterCamera& cam, const 
           "gsr_loss_backward");
     // rasterizer backward (the gradients w.r.t. the ACTIVATED values; Adam applies the
     // activations' backward in-kernel)
-    auto fo = params_["xyz"].options();
-    auto g_means2D = torch::empty({P, 3}, fo), g_conic = torch::empty({P, 3}, fo), g_opac = torch::empty({P, 1}, fo),
-         g_means3D = torch::empty({P, 3}, fo), g_dc = torch::empty({P, 1, 3}, fo), g_scales = torch::empty({P, 3}, fo),
-         g_rots = torch::empty({P, 4}, fo);
-    const auto& rest = params_["f_rest"];
-    torch::Tensor g_rest = rest.size(1) ? torch::empty_like(rest) : torch::Tensor();
-    gsr_grads gg{};
-    gg.dL_dmeans2D = fp(g_means2D);
-    gg.dL_dconic = fp(g_conic);
-    gg.dL_dopacity = fp(g_opac);
-    gg.dL_dmeans3D = fp(g_means3D);
-    gg.dL_dsh_dc = fp(g_dc);
-    gg.dL_dsh_rest = fp(g_rest);
-    gg.dL_dscales = fp(g_scales);
-    gg.dL_drotations = fp(g_rots);
-    RasterSettings rs;
-    rs.bg = bg;
-    rs.sh_degree = active_sh_degree_;
-    detail::backward(fr, rs, params_["xyz"], params_["f_dc"], rest.size(1) ? rest : torch::Tensor(), torch::Tensor(),
-                     o, s, q, torch::Tensor(), dimg, gg);
+    const detail::LeafGrads lg(in, P, /*want_conic=*/true);
+    detail::backward(fr, rs, in, dimg, lg.gg);
     std::map<std::string, torch::Tensor> grads{
-        {"xyz", g_means3D}, {"f_dc", g_dc}, {"opacity", g_opac}, {"scaling", g_scales}, {"rotation", g_rots}};
-    if (rest.size(1)) grads["f_rest"] = g_rest;
+        {"xyz", lg.means3D}, {"f_dc", lg.dc}, {"opacity", lg.opac}, {"scaling", lg.scales}, {"rotation", lg.rots}};
+    if (lg.rest.defined()) grads["f_rest"] = lg.rest;
     std::vector<std::string> replaced;
     if (iteration < opt_.densify_until_iter_) {
-        check(gsr_densify_stats_guarded(fr.radii.data_ptr<int32_t>(), fp(g_means2D), (int32_t)P, fp(max_radii2D_),
+        check(gsr_densify_stats_guarded(fr.radii.data_ptr<int32_t>(), fp(lg.means2D), (int32_t)P, fp(max_radii2D_),
                                         fp(xyz_gradient_accum_), fp(denom_), guard_ptr(), (uint32_t)guard_cap_,
                                         stream()),
               "gsr_densify_stats");

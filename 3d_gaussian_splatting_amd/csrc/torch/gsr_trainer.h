@@ -142,8 +142,8 @@ class Trainer {
     BinningCapacity& binning() { return binning_; }
 
    private:
-    detail::Frame render(const RasterCamera& cam, const std::array<float, 3>& bg, torch::Tensor& s,
-                         torch::Tensor& q, torch::Tensor& o);
+    // activates the parameters into `in`, completes `rs` (SH degree, binning bound) and renders
+    detail::Frame render(const RasterCamera& cam, RasterSettings& rs, detail::Inputs& in);
     void setup();
     void optimizer_step(const std::map<std::string, torch::Tensor>& grads);
     const uint32_t* guard_ptr() const {

@@ -1,7 +1,7 @@
 // dropin_main.cpp -- gsr::render() compiled against the reference's own call surface and run
 // for one training step: render -> L1 -> backward -> one Adam step per parameter group, the loop
 // body src/utils/train_utils.cpp:128-145 leaves out.  Built by __graft_entry__.build() (g++,
-// libtorch, -DGSR_NO_PYBIND, libgsr_hip.so) into 3d_gaussian_splatting_amd/lib/gsr_dropin and run
+// libtorch, the layer's objects, libgsr_hip.so) into 3d_gaussian_splatting_amd/lib/gsr_dropin and run
 // by tests/test_gpu_dropin.py, which compares every output with the C-ABI path.
 //
 // GaussianModel, PipelineParams and Camera below are stand-ins that reproduce the reference's

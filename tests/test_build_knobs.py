@@ -19,7 +19,6 @@ KNOBS = {
     "GSR_PRESORT_PER_TILE",
     "GSR_BLOCK8_TILES",
 }
-NOT_KERNEL_KNOBS = {"GSR_NO_PYBIND"}  # the libtorch layer without its Python binding (C++ executables)
 
 
 def source_knobs():
@@ -31,7 +30,7 @@ def source_knobs():
         lines = open(path).read().split("\n")
         for i, line in enumerate(lines):
             m = re.match(r"\s*#\s*ifndef\s+(GSR_\w+)\s*$", line)
-            if not m or m.group(1) in NOT_KERNEL_KNOBS:
+            if not m:
                 continue
             d = re.match(r"\s*#\s*define\s+%s\s+(.*?)\s*$" % m.group(1), lines[i + 1])
             assert d, f"{path}:{i + 1}: #ifndef {m.group(1)} without its #define on the next line"

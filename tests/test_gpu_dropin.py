@@ -1,5 +1,5 @@
-"""GPU: the C++ drop-in (lib/gsr_dropin, built from tests/cpp/dropin_main.cpp + gsr_torch.cpp with
--DGSR_NO_PYBIND) -- gsr::render<GaussianModel, PipelineParams>() compiled against the
+"""GPU: the C++ drop-in (lib/gsr_dropin, built from tests/cpp/dropin_main.cpp + the libtorch layer
+without gsr_bind.cpp) -- gsr::render<GaussianModel, PipelineParams>() compiled against the
 reference's exact getter / PipelineParams / Camera surface -- runs one render -> L1 -> backward
 -> Adam step, and every output equals the same step through the C ABI (CAbiRasterizer) with
 torch autograd for the activations and torch.optim.Adam for the update.

@@ -229,3 +229,65 @@ def test_plan_from_stats_exact():
         c_rows, c_max, c_k = ext.plan_from_stats([int(v) for v in inst], [[int(v) for v in x[2]] for x in shards],
                                                  [[int(v) for v in x[3]] for x in shards], world)
         assert list(c_rows) == rows and c_max == max_splats and list(c_k) == band_k
+
+
+def _plan_cases():
+    """(input line, expected output line from bands.py) of tests/cpp/plan_main.cpp."""
+    bands = pkg("bands")
+    rng = np.random.default_rng(11)
+    words = lambda v: " ".join(str(int(x)) for x in v)
+    cases = []
+
+    def plan_case(inst, shards, world):
+        gy = len(inst)
+        rows, max_splats, band_k = bands.plan_from_stats(inst, [s for s, _ in shards], [e for _, e in shards], world)
+        line = f"plan {world} {gy} {len(shards)} {words(inst)} " + " ".join(f"{words(s)} {words(e)}" for s, e in shards)
+        cases.append((line, f"{words(rows)} | {max_splats} | {words(band_k)}"))
+        cases.append((f"balance {world} {gy} {words(inst)}", words(bands.balance_bands(inst, world))))
+
+    for world in (1, 2, 4, 8):
+        for gy in (world, 9, 68):  # gy == world: one tile row per band
+            cases.append((f"equal {gy} {world}", words(bands.equal_bands(gy, world))))
+            inst = np.zeros(gy, np.int64)
+            shards = []
+            for _ in range(world):  # random rects: a random histogram and consistent starts / ends
+                miny, maxy = _rect_rows(rng, int(rng.integers(0, 3000)), gy)
+                for a, b_, w in zip(miny, maxy, rng.integers(1, 6, miny.size)):
+                    inst[a:b_] += w
+                shards.append((np.bincount(miny, minlength=gy), np.bincount(maxy - 1, minlength=gy)))
+            plan_case(inst, shards, world)
+            zero = np.zeros(gy, np.int64)
+            plan_case(zero, [(zero, zero)] * world, world)  # nothing visible: the equal cuts
+            one = zero.copy()
+            one[int(rng.integers(0, gy))] = 12345  # all mass in one tile row
+            plan_case(one, [(one // 5, one // 5)] * world, world)
+    for rank in range(4):
+        cases.append((f"shard 10 4 {rank}", words(bands.gaussian_shard(10, 4, rank))))
+    assert bands.gaussian_shard(10, 4, 3) == (9, 10) and bands.gaussian_shard(10, 4, 0) == (0, 3)
+    return cases
+
+
+def test_plan_cpp_is_free_standing_and_exact(tmp_path):
+    """csrc/torch/gsr_plan.cpp compiles with plain g++ -std=c++17 and only its own directory on
+    the include path (no torch, no HIP: the compile is the assertion), and the program built from
+    it and tests/cpp/plan_main.cpp agrees exactly with bands.py: plan_from_stats (rows, max_splats,
+    band_k), gaussian_shard, equal_bands and balance_bands, for world 1 / 2 / 4 / 8 x grid_y = world /
+    9 / 68 with random, all-zero and single-row histograms."""
+    import shutil
+    import subprocess
+    from conftest import ROOT
+    cxx = shutil.which("g++")
+    assert cxx, "g++ not found"
+    tdir = os.path.join(ROOT, "3d_gaussian_splatting_amd", "csrc", "torch")
+    exe = str(tmp_path / "plan_main")
+    r = subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", "-I", tdir, os.path.join(tdir, "gsr_plan.cpp"),
+                        os.path.join(ROOT, "tests", "cpp", "plan_main.cpp"), "-o", exe],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    cases = _plan_cases()
+    r = subprocess.run([exe], input="\n".join(c for c, _ in cases) + "\n", capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    got = r.stdout.strip().split("\n")
+    assert len(got) == len(cases)
+    for (case, want), line in zip(cases, got):
+        assert line.strip() == want, case[:80]
