@@ -6,7 +6,7 @@
 
 The libtorch layer (csrc/torch/) is compiled once, position-independent, into lib/obj/*.o; the
 extension links those objects plus gsr_bind.cpp (the only pybind11 file), the executables link
-them plus gsr_trainer.cpp and their main.
+them plus their main.
 
 Per-file flags: gsr_preprocess.hip is compiled with -ffp-contract=off so its key-feeding
 arithmetic is bit-identical to the CPU oracle; the blend and preprocess-backward files too
@@ -209,11 +209,11 @@ def _exe_flags():
     return flags, libs
 
 
-# the libtorch layer: LAYER_SOURCES go into the extension and the C++ executables alike (compiled
-# once, -fPIC), the trainer into the executables only
+# the libtorch layer: LAYER_SOURCES go into the extension (which binds the trainer's depth_loss)
+# and the C++ executables alike (compiled once, -fPIC)
 LAYER_SOURCES = [os.path.join(CSRC, "torch", f) for f in ("gsr_torch.cpp", "gsr_exchange.cpp", "gsr_plan.cpp",
-                                                          "gsr_shard.cpp")]
-EXE_LIB_SOURCES = LAYER_SOURCES + [os.path.join(CSRC, "torch", "gsr_trainer.cpp")]
+                                                          "gsr_shard.cpp", "gsr_trainer.cpp")]
+EXE_LIB_SOURCES = LAYER_SOURCES
 EXE_HEADERS = [os.path.join(CSRC, "torch", h) for h in ("gsr_render.h", "gsr_trainer.h", "gsr_shard.h",
                                                         "gsr_exchange.h", "gsr_plan.h")]
 

@@ -11,6 +11,10 @@
 //                         partial per block (fixed-order sums, no atomics).
 //  * ssim_backward_kernel the adjoint: blur of the three maps (same separable window) combined
 //                         with x and y, plus the L1 sign term -> dL/dimg.
+//  * depth_loss_kernel    weight * mean |(pred - target) * mask| over an H x W depth plane (pred = the
+//                         blended depth, or depth / alpha) and dL/ddepth, dL/dalpha in the same pass:
+//                         float4 per thread, one (sum |e|, count) partial per block, summed in
+//                         double by depth_loss_finalize_kernel (fixed order, no atomics).
 //  * adam_kernel          one launch for all six parameter groups (multi-tensor): activation
 //                         backward, moments, bias-corrected update; float4 per thread.
 //  * densify_stats_kernel max_radii2D / grad accumulation / denom for radii > 0.
@@ -289,6 +293,141 @@ __global__ __launch_bounds__(256) void ssim_backward_kernel(const float* __restr
         const float d = x - y;
         const float sgn = d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f);
         dimg[o] = fmaf(l1scale, sgn, mv[j][0] + 2.0f * x * mv[j][1] + y * mv[j][2]);
+    }
+}
+
+// ---------------------------------------------------------------- depth L1
+// weight * mean |(pred - target) * mask| and its gradient in one pass (the gradient of an L1 mean
+// does not depend on the sum): a block takes chunks of 256 x 4 consecutive pixels, chunk c of
+// block b being b + c * gridDim.x, and the grid depends on H * W alone, so the partial sums and
+// their order -- hence the bits -- are a function of the inputs only.
+constexpr int kDepthBlock = 256, kDepthChunk = 4 * kDepthBlock, kDepthMaxBlocks = 2048;
+
+struct DepthLossArgs {
+    const float* depth;
+    const float* alpha;   // NORMALIZED only
+    const float* target;
+    const float* mask;    // nullable: 1
+    float* d_depth;
+    float* d_alpha;       // NORMALIZED only
+    long long n;
+    float gscale;         // weight / n
+    float alpha_min;
+    int mode;
+};
+
+__host__ __device__ inline long long depth_loss_chunks(long long n) { return (n + kDepthChunk - 1) / kDepthChunk; }
+inline int depth_loss_blocks(long long n) {
+    const long long c = depth_loss_chunks(n);
+    return (int)(c < kDepthMaxBlocks ? (c > 0 ? c : 1) : kDepthMaxBlocks);
+}
+
+// V4: a full group of 4 pixels on 16-byte-aligned planes (one float4 access per plane); otherwise
+// `cnt` <= 4 pixels with scalar accesses.
+template <bool V4>
+__device__ __forceinline__ void depth_load4(const float* p, long long e0, int cnt, float (&v)[4]) {
+    if (V4) {
+        const float4 q = *reinterpret_cast<const float4*>(p + e0);
+        v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = k < cnt ? p[e0 + k] : 0.f;
+    }
+}
+
+template <bool V4>
+__device__ __forceinline__ void depth_store4(float* p, long long e0, int cnt, const float (&v)[4]) {
+    if (V4) {
+        *reinterpret_cast<float4*>(p + e0) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (k < cnt) p[e0 + k] = v[k];
+    }
+}
+
+// the pixels e0 .. e0 + cnt - 1 of one thread: gradients out, (sum |e|, count) into the thread's sums
+template <bool V4>
+__device__ __forceinline__ void depth_loss_group(const DepthLossArgs& a, long long e0, int cnt, float& asum,
+                                                 float& cnt_sum) {
+#pragma clang fp contract(off)  // both instantiations round alike: float4 and scalar paths, same bits
+    const bool norm = a.mode == GSR_DEPTH_NORMALIZED;
+    float d[4], t[4], m[4], al[4] = {0.f, 0.f, 0.f, 0.f}, gd[4], ga[4];
+    depth_load4<V4>(a.depth, e0, cnt, d);
+    depth_load4<V4>(a.target, e0, cnt, t);
+    if (a.mask) {
+        depth_load4<V4>(a.mask, e0, cnt, m);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) m[k] = k < cnt ? 1.f : 0.f;
+    }
+    if (norm) depth_load4<V4>(a.alpha, e0, cnt, al);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        // a pixel below alpha_min (alpha_min > 0, so alpha = 0 never divides) contributes nothing
+        const bool ok = !norm || al[k] >= a.alpha_min;
+        const float inv = norm ? (ok ? 1.0f / al[k] : 0.f) : 1.0f;
+        const float mk = ok ? m[k] : 0.f;
+        const float pred = norm ? d[k] * inv : d[k];
+        const float e = ok ? (pred - t[k]) * mk : 0.f;
+        const float sgn = e > 0.f ? 1.f : (e < 0.f ? -1.f : 0.f);
+        const float gp = a.gscale * mk * sgn;  // dL/dpred
+        gd[k] = gp * inv;
+        ga[k] = ok ? -gp * d[k] * inv * inv : 0.f;
+        asum += fabsf(e);
+        cnt_sum += mk != 0.f ? 1.f : 0.f;
+    }
+    depth_store4<V4>(a.d_depth, e0, cnt, gd);
+    if (norm) depth_store4<V4>(a.d_alpha, e0, cnt, ga);
+}
+
+// VEC: every plane is 16-byte aligned, so the full groups of 4 move as float4; otherwise (and for
+// the image's last, partial group) the same thread moves the same pixels with scalar accesses, so
+// both paths sum alike.
+template <bool VEC>
+__global__ __launch_bounds__(kDepthBlock) void depth_loss_kernel(const DepthLossArgs a, float2* __restrict__ part) {
+    __shared__ float red[8];
+    const long long chunks = depth_loss_chunks(a.n);
+    float asum = 0.f, cnt_sum = 0.f;
+    for (long long c = blockIdx.x; c < chunks; c += gridDim.x) {
+        const long long e0 = c * kDepthChunk + 4 * (long long)threadIdx.x;
+        const long long left = a.n - e0;
+        if (left <= 0) continue;
+        if (VEC && left >= 4)
+            depth_loss_group<true>(a, e0, 4, asum, cnt_sum);
+        else
+            depth_loss_group<false>(a, e0, left < 4 ? (int)left : 4, asum, cnt_sum);
+    }
+    block_sum2(asum, cnt_sum, red);
+    if (threadIdx.x == 0) part[blockIdx.x] = make_float2(asum, cnt_sum);
+}
+
+// one block: the partials in double, in index order per thread and a fixed tree across threads
+__global__ __launch_bounds__(256) void depth_loss_finalize_kernel(const float2* __restrict__ part, int nparts,
+                                                                  double inv_n, float weight,
+                                                                  float* __restrict__ stats) {
+    __shared__ double rs[256], rc[256];
+    double s = 0.0, c = 0.0;
+    for (int i = threadIdx.x; i < nparts; i += 256) {
+        const float2 p = part[i];
+        s += (double)p.x;
+        c += (double)p.y;
+    }
+    rs[threadIdx.x] = s;
+    rc[threadIdx.x] = c;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) {
+            rs[threadIdx.x] += rs[threadIdx.x + o];
+            rc[threadIdx.x] += rc[threadIdx.x + o];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const float l1 = (float)(rs[0] * inv_n);
+        stats[0] = weight * l1;
+        stats[1] = l1;
+        stats[2] = (float)rc[0];
     }
 }
 
@@ -583,6 +722,48 @@ int gsr_loss_backward(const float* img, const float* gt, int32_t C, int32_t H, i
     const float l1scale = (float)((1.0 - (double)lambda_dssim) / (double)n);
     hipLaunchKernelGGL(ssim_backward_kernel, grid, dim3(256), 0, (hipStream_t)stream, img, gt, H, W, ssim_window(),
                        l1scale, static_cast<const float*>(maps), dL_dimg);
+    return (int)hipGetLastError();
+}
+
+size_t gsr_depth_loss_scratch_bytes(int32_t H, int32_t W) {
+    const long long n = (long long)(H > 0 ? H : 0) * (W > 0 ? W : 0);
+    return align256((size_t)depth_loss_blocks(n) * sizeof(float2));
+}
+
+int gsr_depth_loss(const float* depth, const float* alpha, const float* target, const float* mask, int32_t H,
+                   int32_t W, float weight, int32_t mode, float alpha_min, void* scratch, float* stats,
+                   float* dL_ddepth, float* dL_dalpha, void* stream) {
+    if (H <= 0 || W <= 0) return set_error(-1, "depth loss: bad image shape");
+    if (!depth || !target || !scratch || !stats || !dL_ddepth) return set_error(-1, "depth loss: null pointer");
+    if (reinterpret_cast<uintptr_t>(scratch) & 7) return set_error(-1, "depth loss: scratch must be 8-byte aligned");
+    if (mode != GSR_DEPTH_RAW && mode != GSR_DEPTH_NORMALIZED) return set_error(-1, "depth loss: unknown mode");
+    const bool norm = mode == GSR_DEPTH_NORMALIZED;
+    if (norm && (!alpha || !dL_dalpha)) return set_error(-1, "depth loss: normalized mode needs alpha and dL_dalpha");
+    if (norm && !(alpha_min > 0.0f)) return set_error(-1, "depth loss: alpha_min must be > 0");
+    if (!(weight >= 0.0f) || std::isinf(weight)) return set_error(-1, "depth loss: weight must be finite and >= 0");
+    DepthLossArgs a;
+    a.depth = depth;
+    a.alpha = norm ? alpha : nullptr;
+    a.target = target;
+    a.mask = mask;
+    a.d_depth = dL_ddepth;
+    a.d_alpha = norm ? dL_dalpha : nullptr;
+    a.n = (long long)H * W;
+    a.gscale = (float)((double)weight / (double)a.n);
+    a.alpha_min = alpha_min;
+    a.mode = mode;
+    bool vec = true;  // the ABI takes any 4-byte-aligned plane; float4 accesses need all of them at 16
+    for (const void* p : {(const void*)a.depth, (const void*)a.alpha, (const void*)a.target, (const void*)a.mask,
+                          (const void*)a.d_depth, (const void*)a.d_alpha})
+        if (reinterpret_cast<uintptr_t>(p) & 15) vec = false;
+    const int nb = depth_loss_blocks(a.n);
+    float2* part = static_cast<float2*>(scratch);
+    hipStream_t s = (hipStream_t)stream;
+    if (vec)
+        hipLaunchKernelGGL(depth_loss_kernel<true>, dim3(nb), dim3(kDepthBlock), 0, s, a, part);
+    else
+        hipLaunchKernelGGL(depth_loss_kernel<false>, dim3(nb), dim3(kDepthBlock), 0, s, a, part);
+    hipLaunchKernelGGL(depth_loss_finalize_kernel, dim3(1), dim3(256), 0, s, part, nb, 1.0 / (double)a.n, weight, stats);
     return (int)hipGetLastError();
 }
 

@@ -1,5 +1,6 @@
 // gsr_bind.cpp -- the Python binding (_gsr_torch) of the libtorch layer: the rasterizer entry
-// points of gsr_render.h and the multi-GPU step of gsr_shard.h (the benchmark's multi-GPU path).
+// points of gsr_render.h, the depth loss of gsr_trainer.h and the multi-GPU step of gsr_shard.h
+// (the benchmark's multi-GPU path).
 // The only file of the layer that includes pybind11; a C++ executable links the others without it.
 #include <pybind11/stl.h>
 #include <torch/extension.h>
@@ -7,6 +8,7 @@
 
 #include "gsr_render.h"
 #include "gsr_shard.h"
+#include "gsr_trainer.h"
 
 namespace py = pybind11;
 
@@ -202,6 +204,16 @@ PYBIND11_MODULE(_gsr_torch, m) {
         py::arg("cam"), py::arg("settings"), py::arg("inverse_depth"), py::arg("means3D"), py::arg("means2D"),
         py::arg("sh_dc"), py::arg("sh_rest"), py::arg("colors_precomp"), py::arg("opacities"), py::arg("scales"),
         py::arg("rotations"), py::arg("cov3D_precomp"));
+    m.def(
+        "depth_loss",
+        [](torch::Tensor depth, OptTensor alpha, torch::Tensor target, OptTensor mask, double weight, int mode,
+           double alpha_min) {
+            torch::Tensor stats;
+            auto loss = gsr::depth_loss(depth, opt(alpha), target, opt(mask), weight, mode, alpha_min, &stats);
+            return py::make_tuple(loss, stats);
+        },
+        py::arg("depth"), py::arg("alpha"), py::arg("target"), py::arg("mask"), py::arg("weight") = 1.0,
+        py::arg("mode") = GSR_DEPTH_RAW, py::arg("alpha_min") = 0.5);
     m.def("eval_sh_colors", &gsr::eval_sh_colors);
     m.def(
         "camera_from_tensors",

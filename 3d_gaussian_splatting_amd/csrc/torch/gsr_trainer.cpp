@@ -64,6 +64,49 @@ class PhotometricLoss : public torch::autograd::Function<PhotometricLoss> {
     }
 };
 
+// ---- depth loss autograd Function ----
+class DepthLoss : public torch::autograd::Function<DepthLoss> {
+   public:
+    static variable_list forward(AutogradContext* ctx, torch::Tensor depth, torch::Tensor alpha, torch::Tensor target,
+                                 torch::Tensor mask, double weight, int64_t mode, double alpha_min) {
+        TORCH_CHECK(depth.dim() == 2, "depth loss: depth must be (H,W)");
+        const bool norm = mode == GSR_DEPTH_NORMALIZED;
+        // absent alpha / mask arrive as 0-element tensors (Function::apply rejects undefined ones)
+        TORCH_CHECK(!norm || alpha.numel() > 0, "depth loss: normalized mode needs alpha");
+        auto plane = [&](const torch::Tensor& t, const char* what) {
+            if (!t.defined() || t.numel() == 0) return torch::Tensor();
+            TORCH_CHECK(t.sizes() == depth.sizes(), "depth loss: ", what, " must match depth's (H,W)");
+            auto c = t.contiguous();
+            require_f32(c, what);
+            return c;
+        };
+        auto d = plane(depth, "depth"), t = plane(target, "target"), m = plane(mask, "mask");
+        auto a = norm ? plane(alpha, "alpha") : torch::Tensor();
+        TORCH_CHECK(t.defined(), "depth loss: target is required");
+        const int H = (int)d.size(0), W = (int)d.size(1);
+        auto scratch = torch::empty({(int64_t)gsr_depth_loss_scratch_bytes(H, W)}, d.options().dtype(torch::kUInt8));
+        auto stats = torch::empty({3}, d.options());
+        auto dd = torch::empty_like(d);
+        auto da = norm ? torch::empty_like(d) : torch::Tensor();
+        check(gsr_depth_loss(fp(d), fp(a), fp(t), fp(m), H, W, (float)weight, (int32_t)mode, (float)alpha_min,
+                             scratch.data_ptr(), fp(stats), fp(dd), fp(da), stream()),
+              "gsr_depth_loss");
+        ctx->save_for_backward({dd, norm ? da : torch::empty({0}, d.options())});
+        ctx->mark_non_differentiable({stats});
+        return {stats.select(0, 0).clone(), stats};
+    }
+
+    static variable_list backward(AutogradContext* ctx, variable_list grad_out) {
+        auto sv = ctx->get_saved_variables();
+        auto dd = sv[0], da = sv[1].numel() ? sv[1] : torch::Tensor();
+        if (grad_out[0].defined()) {  // dL/dloss (a device scalar, no host read)
+            dd = dd * grad_out[0];
+            if (da.defined()) da = da * grad_out[0];
+        }
+        return {dd, da, torch::Tensor(), torch::Tensor(), torch::Tensor(), torch::Tensor(), torch::Tensor()};
+    }
+};
+
 }  // namespace
 
 std::function<double(int)> get_expon_lr_func(double lr_init, double lr_final, int lr_delay_steps,
@@ -82,6 +125,15 @@ std::function<double(int)> get_expon_lr_func(double lr_init, double lr_final, in
 torch::Tensor photometric_loss(const torch::Tensor& image, const torch::Tensor& gt, double lambda_dssim,
                                torch::Tensor* stats) {
     auto outs = PhotometricLoss::apply(image, gt, lambda_dssim);
+    if (stats) *stats = outs[1];
+    return outs[0];
+}
+
+torch::Tensor depth_loss(const torch::Tensor& depth, const torch::Tensor& alpha, const torch::Tensor& target,
+                         const torch::Tensor& mask, double weight, int mode, double alpha_min, torch::Tensor* stats) {
+    auto none = torch::empty({0}, depth.options());
+    auto outs = DepthLoss::apply(depth, alpha.defined() ? alpha : none, target, mask.defined() ? mask : none, weight,
+                                 (int64_t)mode, alpha_min);
     if (stats) *stats = outs[1];
     return outs[0];
 }

@@ -14,7 +14,10 @@
 // 2. gsr::Trainer: the same iteration without autograd (activations and their backward fused
 //    into the kernels, no per-op launches), densification and opacity reset included -- the
 //    native twin of 3d_gaussian_splatting_amd/trainer.py (GaussianTrainer), op for op, so a loop
-//    over it reproduces the Python loop bit for bit (tests/test_gpu_train_loop.py).
+//    over it reproduces the Python loop bit for bit (tests/test_gpu_train_loop.py).  It trains on
+//    colour only: depth supervision (gsr::depth_loss below, GaussianTrainer.step(gt_depth=...) in
+//    Python) is not part of Trainer::step or the gsr_train_loop executable, whose scene file
+//    carries no depth targets.
 //
 // OptimizationParams is the reference's struct (src/arguments/params.h:50-91: same fields,
 // float types and defaults).
@@ -68,6 +71,17 @@ std::function<double(int)> get_expon_lr_func(double lr_init, double lr_final, in
 // `stats`, when given, receives [loss, l1, ssim] (device, 3).  No host wait.
 torch::Tensor photometric_loss(const torch::Tensor& image, const torch::Tensor& gt, double lambda_dssim,
                                torch::Tensor* stats = nullptr);
+
+// weight * mean |(pred - target) * mask| over (H,W) planes (gsr_depth_loss; upstream 3DGS's depth
+// regulariser) for the depth / alpha outputs of gsr::render(..., return_depth): pred = depth
+// (GSR_DEPTH_RAW) or depth / alpha where alpha >= alpha_min (GSR_DEPTH_NORMALIZED).  `alpha` (RAW)
+// and `mask` may be undefined tensors.  An autograd Function, differentiable in depth and alpha:
+// value and gradients come from the one kernel pass of the forward, the backward scales them by
+// the incoming gradient on the device.  Returns the scalar weighted loss on the device; `stats`,
+// when given, receives [weighted loss, mean |e|, contributing pixels] (device, 3).  No host wait.
+torch::Tensor depth_loss(const torch::Tensor& depth, const torch::Tensor& alpha, const torch::Tensor& target,
+                         const torch::Tensor& mask, double weight, int mode = GSR_DEPTH_RAW,
+                         double alpha_min = 0.5, torch::Tensor* stats = nullptr);
 
 // One step of every given torch::optim::Adam, fused into ONE gsr_adam_step launch over all
 // their parameters, on libtorch's own state (AdamParamState exp_avg / exp_avg_sq / step, created

@@ -596,6 +596,19 @@ def rasterize_gaussians(cam: RasterCamera, means3D, means2D, opacities, sh_dc=No
                                    opacities, scales, rotations, cov3D_precomp)
 
 
+def depth_loss(depth, target, mask=None, alpha=None, weight=1.0, normalized=False, alpha_min=0.5,
+               return_stats=False):
+    """weight * mean |(pred - target) * mask| over (H, W) planes, for the "depth" / "alpha" keys of
+    render(return_depth=True): pred = depth, or with `normalized` depth / alpha where
+    alpha >= alpha_min (other pixels contribute nothing).  One fused HIP pass (gsr_depth_loss)
+    behind a libtorch autograd Function, differentiable in depth and alpha; returns the scalar loss
+    on the device (with return_stats also [weighted loss, mean |e|, contributing pixels])."""
+    ext = native.load_torch_ext()
+    loss, stats = ext.depth_loss(depth, alpha, target, mask, float(weight),
+                                 native.DEPTH_NORMALIZED if normalized else native.DEPTH_RAW, float(alpha_min))
+    return (loss, stats) if return_stats else loss
+
+
 @dataclass
 class PipelineParams:
     """Mirror of src/arguments/params.h:93-106."""

@@ -26,11 +26,16 @@ nothing here is on the GPU hot path.  What each function restates:
     (src/scene/gaussian_model.cpp:76-202): the CoreParams tensor list in the reference's order
     plus each parameter group's Adam state, loadable with torch.load(weights_only=True).
 
+  - ``load_depth_params`` / ``depth_target``: the upstream 3DGS depth regularisation inputs
+    (depth_params.json from utils/make_depth_scale.py, read in scene/dataset_readers.py; the
+    per-image scale / offset and reliability test of scene/cameras.py).  The reference has none.
+
 Images are not decoded (OpenCV is absent here and out of scope): ``CameraInfo`` carries the
 path and ``image`` stays None unless the caller fills it.
 """
 from __future__ import annotations
 
+import json
 import os
 import struct
 from dataclasses import dataclass
@@ -499,6 +504,34 @@ def load_checkpoint(path: str, device="cpu") -> dict:
 
 # ---- point-cloud initialisation constants (upstream sh_utils / general_utils) ----
 SH_C0 = 0.28209479177387814
+
+
+# ------------------------------------------------------------------------------------------
+# depth supervision inputs (upstream 3DGS)
+# ------------------------------------------------------------------------------------------
+def load_depth_params(path: str) -> dict[str, dict]:
+    """Upstream's depth_params.json: {image_name: {"scale": s, "offset": o}, ...}, the affine map
+    from a monocular inverse-depth image to the COLMAP scene's inverse depth.  As upstream's
+    readColmapSceneInfo, every entry also gets "med_scale", the median of the positive scales
+    (0.0 when there is none)."""
+    with open(path) as fh:
+        raw = json.load(fh)
+    out = {str(k): {"scale": float(v["scale"]), "offset": float(v["offset"])} for k, v in raw.items()}
+    scales = np.array([v["scale"] for v in out.values()], np.float64)
+    med = float(np.median(scales[scales > 0])) if (scales > 0).any() else 0.0
+    for v in out.values():
+        v["med_scale"] = med
+    return out
+
+
+def depth_target(raw, scale: float, offset: float, med_scale: float):
+    """-> (raw * scale + offset as f32, reliable): the inverse-depth target of one image and
+    upstream's reliability test 0.2 * med_scale <= scale <= 5 * med_scale (upstream zeroes the
+    depth mask of an unreliable image: pass depth_mask = 0, or no target, for it).  `raw` is the
+    decoded monocular inverse-depth image as an array; no image is decoded here."""
+    target = np.asarray(raw, np.float32) * np.float32(scale) + np.float32(offset)
+    reliable = bool(0.2 * med_scale <= scale <= 5.0 * med_scale)
+    return target, reliable
 
 
 def rgb2sh(rgb):

@@ -9,7 +9,8 @@ statistics, densify / prune every ``densification_interval`` iterations in
 [``densify_from_iter``, ``densify_until_iter``), opacity reset every ``opacity_reset_interval``,
 then the fused Adam step -- with the OptimizationParams defaults of src/arguments/params.h:50-91.
 No host synchronisation inside an iteration except the densification read-backs; the loss is
-read back only at the log points.
+read back only at the log points.  A scene that carries per-view depth targets adds upstream's
+depth term to every iteration (``GaussianTrainer.step(gt_depth=...)``).
 
 The scene: ground-truth images rendered by the same rasterizer from a procedural cloud of
 Gaussians (a textured ground disc and a few object blobs, SH degree 1) seen by cameras on an
@@ -30,7 +31,7 @@ import torch
 from . import graphics
 from .rasterizer import CAbiRasterizer
 from .scene import normal, uniform
-from .trainer import GaussianTrainer, OptimizationParams
+from .trainer import GaussianTrainer, OptimizationParams, TrainKernels
 
 
 @dataclass
@@ -41,6 +42,8 @@ class LoopScene:
     colors: np.ndarray   # (n, 3) its colours in [0, 1]
     extent: float        # camera extent (nerf++ radius), spatial_lr_scale upstream
     n_gt: int = 0
+    depths: list | None = None       # (H, W) f32 device tensors: per-view depth targets (inverse depth)
+    depth_masks: list | None = None  # (H, W) f32 device tensors, or None for all ones
 
 
 def look_at_camera(center, target, fovx: float, width: int, height: int) -> graphics.RasterCamera:
@@ -111,9 +114,12 @@ def procedural_cloud(n: int, seed: int = 0, texture: float = 0.25, gt_scale: flo
 
 
 def synthetic_scene(n_gt: int, n_init: int, n_views: int, width: int, height: int, seed: int = 0,
-                    device="cuda", texture: float = 0.25, gt_scale: float = 0.012) -> LoopScene:
+                    device="cuda", texture: float = 0.25, gt_scale: float = 0.012,
+                    with_depth: bool = False) -> LoopScene:
     """Ground truth rendered once per view (the rasterizer's forward, no gradients), and a
-    sparse noisy initial point cloud."""
+    sparse noisy initial point cloud.  with_depth: every view also gets a depth target, the
+    ground-truth cloud's blended inverse depth (forward_aux(inverse_depth=True).depth, un-normalised
+    like upstream's invDepth); the colour targets are the same with and without it."""
     means, f_dc, f_rest, opac, log_s, q, rgb = procedural_cloud(n_gt, seed, texture, gt_scale)
     cams = orbit_cameras(n_views, width, height, seed=seed)
     dev = torch.device(device)
@@ -121,15 +127,23 @@ def synthetic_scene(n_gt: int, n_init: int, n_views: int, width: int, height: in
     sc, qq = torch.exp(t(log_s)), torch.nn.functional.normalize(t(q), dim=1)
     op = torch.sigmoid(t(opac)).reshape(-1)
     rast = CAbiRasterizer(dev)
-    gts = []
+    gts, depths = [], []
+    if with_depth:  # the activations a trainer applies to these leaves (gsr_activate), so that a
+        # trainer holding the ground-truth leaves renders the targets bit for bit
+        sa, qa, oa = TrainKernels(dev).activate(t(log_s), t(q), t(opac))
     for cam in cams:
         st = rast.forward(cam, t(means), op, scales=sc, rotations=qq, sh_dc=t(f_dc), sh_rest=t(f_rest), sh_degree=1)
         gts.append(st.color.clamp(0.0, 1.0).contiguous())
+        if with_depth:
+            sd = rast.forward_aux(cam, t(means), oa.reshape(-1), scales=sa, rotations=qa, sh_dc=t(f_dc),
+                                  sh_rest=t(f_rest), sh_degree=1, inverse_depth=True)
+            depths.append(sd.depth.contiguous())
     pick = (uniform(seed, 31, n_init) * n_gt).astype(np.int64)
     pts = means[pick] + 0.02 * normal(seed, 32, 3 * n_init).reshape(n_init, 3).astype(np.float32)
     centres = np.stack([c.campos for c in cams]).astype(np.float64)
     extent = float(np.linalg.norm(centres - centres.mean(0), axis=1).max() * 1.1)  # get_nerfpp_norm radius
-    return LoopScene(cams=cams, gts=gts, points=pts.astype(np.float32), colors=rgb[pick], extent=extent, n_gt=n_gt)
+    return LoopScene(cams=cams, gts=gts, points=pts.astype(np.float32), colors=rgb[pick], extent=extent, n_gt=n_gt,
+                     depths=depths if with_depth else None)
 
 
 @dataclass
@@ -143,6 +157,7 @@ class LoopResult:
     peak_points: int = 0
     binning_overflows: int = 0   # bounded renders whose K exceeded the bound (must stay 0)
     exact_k_reads: int = 0       # renders sized by a host read of K (after each point-set change)
+    depth_loss: list = field(default_factory=list)  # (iteration, weighted loss, mean |e|, pixels) at the log points
 
 
 def view_sequence(n_views: int, iterations: int, seed: int = 0) -> np.ndarray:
@@ -163,6 +178,9 @@ def write_scene(path: str, scene: LoopScene, iterations: int, opt: OptimizationP
                 progress_every: int = 0, views=None) -> None:
     """The GSRLOOP1 file tests/cpp/train_main.cpp (lib/gsr_train_loop) reads: the scene, the
     OptimizationParams (as the reference's float fields) and the camera of every iteration."""
+    if scene.depths is not None:
+        raise ValueError("write_scene: the GSRLOOP1 file has no depth targets (the C++ loop trains on colour only); "
+                         "pass a scene without depths")
     opt = opt or OptimizationParams()
     views = view_sequence(len(scene.cams), iterations, seed) if views is None else np.asarray(views, np.int32)
     H, W = int(scene.gts[0].shape[1]), int(scene.gts[0].shape[2])
@@ -201,14 +219,20 @@ def train(scene: LoopScene, iterations: int | None = None, opt: OptimizationPara
                                           opt=opt, device=device, seed=seed)
     views = view_sequence(len(scene.cams), iterations, seed)
     res = LoopResult(iterations=iterations, seconds=0.0, iters_per_s=0.0)
-    logged = []
+    logged, depth_logged = [], []
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for it in range(1, iterations + 1):
         v = int(views[it - 1])
-        out = tr.step(it, scene.cams[v], scene.gts[v])
+        if scene.depths is not None:
+            out = tr.step(it, scene.cams[v], scene.gts[v], gt_depth=scene.depths[v],
+                          depth_mask=scene.depth_masks[v] if scene.depth_masks is not None else None)
+        else:
+            out = tr.step(it, scene.cams[v], scene.gts[v])
         if it % log_every == 0 or it == 1 or it == iterations:
             logged.append((it, out["stats"]))
+            if "depth_stats" in out:
+                depth_logged.append((it, out["depth_stats"]))
         if it < opt.densify_until_iter and it > opt.densify_from_iter and it % opt.densification_interval == 0:
             res.num_points.append((it, tr.num_points))
         res.peak_points = max(res.peak_points, tr.num_points)
@@ -223,5 +247,6 @@ def train(scene: LoopScene, iterations: int | None = None, opt: OptimizationPara
     res.binning_overflows = tr.binning.overflows
     res.exact_k_reads = tr.binning.exact_reads
     res.loss = [(it, *[float(x) for x in s.cpu().tolist()]) for it, s in logged]
+    res.depth_loss = [(it, *[float(x) for x in s.cpu().tolist()]) for it, s in depth_logged]
     res.trainer = tr
     return res

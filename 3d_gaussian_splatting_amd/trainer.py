@@ -25,7 +25,9 @@ What it mirrors in the reference (seiya-kumada/3d_gaussian_splatting):
 
 Device work per iteration, all through the C ABI: gsr_activate -> gsr_forward -> loss
 forward/backward -> gsr_backward -> gsr_densify_stats -> gsr_adam_step (one launch for the
-six groups, activation backward fused).  No host synchronisation inside ``step`` (the loss
+six groups, activation backward fused); with a depth target (``step(gt_depth=...)``, upstream
+3DGS's depth regulariser -- the reference has none) the render is gsr_forward_aux /
+gsr_backward_aux with gsr_depth_loss between them.  No host synchronisation inside ``step`` (the loss
 stays on the device); densification (every ``densification_interval`` iterations) reads
 counts back.  The forward's binning runs under a capacity bound (``BinningCapacity``), so K is
 not read back either: the first render after a change in the point set is sized exactly (one
@@ -77,6 +79,13 @@ class OptimizationParams:
     densify_until_iter: int = 15_000
     densify_grad_threshold: float = _f32(0.0002)
     random_background: bool = False
+    # depth supervision (upstream 3DGS's depth regulariser; the reference's struct has none):
+    # the weight decays exponentially from _init to _final over `iterations`
+    depth_l1_weight_init: float = 1.0
+    depth_l1_weight_final: float = 0.01
+    depth_inverse: bool = True        # supervise sum w / z (upstream's invDepth)
+    depth_normalized: bool = False    # pred = depth / alpha where alpha >= depth_alpha_min
+    depth_alpha_min: float = 0.5      # a design default, not a tuned value
 
 
 def _device(device) -> torch.device:
@@ -132,6 +141,33 @@ class TrainKernels:
         self._check(self.L.gsr_loss_backward(_p(img), _p(gt), C, H, W, float(lambda_dssim), _p(maps), _p(out),
                                              _stream(self.device)), "gsr_loss_backward")
         return out
+
+    def depth_loss(self, depth, target, mask=None, alpha=None, weight=1.0, normalized=False, alpha_min=0.5):
+        """gsr_depth_loss on (H, W) planes: weight * mean |(pred - target) * mask|, pred = depth or
+        (normalized) depth / alpha where alpha >= alpha_min.  -> (stats (3,) device tensor
+        [weighted loss, mean |e|, contributing pixels], dL_ddepth, dL_dalpha or None), gradients for
+        dL/dloss = 1.  Planes may be any f32 views with contiguous pixels (a 1-element offset takes
+        the kernel's scalar path)."""
+        H, W = (int(v) for v in depth.shape)
+        planes = dict(depth=depth, target=target, mask=mask, alpha=alpha)
+        for name, t in planes.items():
+            if t is None:
+                continue
+            if not (t.is_contiguous() and t.dtype == torch.float32 and t.device == self.device
+                    and tuple(t.shape) == (H, W)):
+                raise ValueError(f"depth_loss: {name} must be a contiguous f32 ({H}, {W}) tensor on {self.device}")
+        if normalized and alpha is None:
+            raise ValueError("depth_loss: normalized mode needs alpha")
+        scratch = torch.empty(int(self.L.gsr_depth_loss_scratch_bytes(H, W)), dtype=torch.uint8, device=self.device)
+        stats = torch.empty(3, dtype=torch.float32, device=self.device)
+        dd = torch.empty_like(depth)
+        da = torch.empty_like(alpha) if normalized else None
+        self._check(self.L.gsr_depth_loss(_p(depth), _p(alpha) if normalized else None, _p(target),
+                                          None if mask is None else _p(mask), H, W, float(weight),
+                                          native.DEPTH_NORMALIZED if normalized else native.DEPTH_RAW,
+                                          float(alpha_min), _p(scratch), _p(stats), _p(dd),
+                                          None if da is None else _p(da), _stream(self.device)), "gsr_depth_loss")
+        return stats, dd, da
 
     def adam_step(self, groups, beta1=0.9, beta2=0.999, eps=1e-8, guard=None):
         """groups: list of dicts(param, grad, exp_avg, exp_avg_sq, act, step, lr), one launch.
@@ -414,6 +450,9 @@ class GaussianTrainer:
                                                opt.position_lr_final * self.spatial_lr_scale,
                                                lr_delay_steps=0, lr_delay_mult=opt.position_lr_delay_mult,
                                                max_steps=opt.position_lr_max_steps)
+        # upstream: depth_l1_weight = get_expon_lr_func(init, final, max_steps=opt.iterations)
+        self.depth_weight_scheduler = get_expon_lr_func(opt.depth_l1_weight_init, opt.depth_l1_weight_final,
+                                                        max_steps=opt.iterations)
 
     def update_learning_rate(self, iteration: int) -> float:
         lr = self.xyz_scheduler(iteration)
@@ -425,19 +464,25 @@ class GaussianTrainer:
             self.active_sh_degree += 1
 
     # ---------------------------------------------------------------- one iteration
-    def render(self, cam, bg=(0.0, 0.0, 0.0)):
+    def render(self, cam, bg=(0.0, 0.0, 0.0), aux: bool = False):
+        """The bounded forward of one iteration; aux: gsr_forward_aux (depth and alpha planes too,
+        inverse depth per opt.depth_inverse) under the same bound and device guard."""
         s, q, o = self.k.activate(self.params["scaling"], self.params["rotation"], self.params["opacity"])
         p = self.params
         bound = self.binning.bound()
-        st = self.rast.forward(cam, p["xyz"], o.reshape(-1), scales=s, rotations=q, sh_dc=p["f_dc"],
-                               sh_rest=p["f_rest"] if p["f_rest"].shape[1] else None,
-                               sh_degree=self.active_sh_degree, bg=bg, max_rendered=bound)
+        kw = dict(scales=s, rotations=q, sh_dc=p["f_dc"], sh_rest=p["f_rest"] if p["f_rest"].shape[1] else None,
+                  sh_degree=self.active_sh_degree, bg=bg, max_rendered=bound)
+        if aux:
+            st = self.rast.forward_aux(cam, p["xyz"], o.reshape(-1), inverse_depth=self.opt.depth_inverse, **kw)
+        else:
+            st = self.rast.forward(cam, p["xyz"], o.reshape(-1), **kw)
         # device-side guard of this iteration's statistics / Adam step (see BinningCapacity)
         self._guard = (st.k_device(), bound) if bound > 0 else None
         self.binning.observe(st)
         return st
 
-    def step(self, iteration: int, cam, gt_image: torch.Tensor, bg=(0.0, 0.0, 0.0), densify: bool = True) -> dict:
+    def step(self, iteration: int, cam, gt_image: torch.Tensor, bg=(0.0, 0.0, 0.0), densify: bool = True,
+             gt_depth: torch.Tensor | None = None, depth_mask: torch.Tensor | None = None) -> dict:
         """One training iteration in the upstream order (train_utils.cpp:128-145 plus the body
         its stub omits): LR update, SH degree, render, loss, backward, densification statistics,
         densify / prune and opacity reset, then the optimizer step.  As upstream, a group whose
@@ -445,15 +490,30 @@ class GaussianTrainer:
         that iteration (torch Adam skips a fresh parameter, whose .grad is None): a densify
         iteration updates no group, an opacity reset alone skips the opacity group.  Returns
         device tensors (loss stats [loss, l1, ssim], radii); no host synchronisation unless a
-        densification is due."""
+        densification is due.
+
+        gt_depth (H, W), with an optional depth_mask (H, W), adds upstream's depth term
+        depth_l1_weight(iteration) * mean |(pred - gt_depth) * depth_mask| (gsr_depth_loss): the
+        render is then forward_aux / backward_aux, pred the blended inverse depth (opt.depth_inverse;
+        divided by alpha with opt.depth_normalized), and the dict gains "depth_stats" ([weighted
+        loss, mean |e|, contributing pixels], device), "depth", "alpha" and "dL_ddepth".  Without a
+        target, or at a scheduled weight of 0, the iteration is the colour-only one, call for call."""
         opt = self.opt
         self.update_learning_rate(iteration)
         if iteration % 1000 == 0:
             self.oneup_SH_degree()
-        st = self.render(cam, bg)
+        depth_weight = self.depth_weight_scheduler(iteration) if gt_depth is not None else 0.0
+        supervised = depth_weight > 0.0
+        st = self.render(cam, bg, aux=supervised)
         stats, maps = self.k.loss_forward(st.color, gt_image, opt.lambda_dssim)
         dimg = self.k.loss_backward(st.color, gt_image, opt.lambda_dssim, maps)
-        g = self.rast.backward(st, dimg)
+        if supervised:
+            depth_stats, dd, da = self.k.depth_loss(st.depth, gt_depth, mask=depth_mask, alpha=st.alpha,
+                                                    weight=depth_weight, normalized=opt.depth_normalized,
+                                                    alpha_min=opt.depth_alpha_min)
+            g = self.rast.backward_aux(st, dimg, dd, da)
+        else:
+            g = self.rast.backward(st, dimg)
         grads = {"xyz": g["means3D"], "f_dc": g["sh_dc"], "opacity": g["opacities"], "scaling": g["scales"],
                  "rotation": g["rotations"]}
         if self.params["f_rest"].shape[1]:
@@ -474,7 +534,10 @@ class GaussianTrainer:
                     replaced.add("opacity")
         if iteration < opt.iterations:
             self.optimizer_step({k: v for k, v in grads.items() if k not in replaced})
-        return {"stats": stats, "radii": st.radii, "state": st, "image": st.color, "num_points": self.num_points}
+        out = {"stats": stats, "radii": st.radii, "state": st, "image": st.color, "num_points": self.num_points}
+        if supervised:
+            out.update(depth_stats=depth_stats, depth=st.depth, alpha=st.alpha, dL_ddepth=dd)
+        return out
 
     def optimizer_step(self, grads: dict):
         groups = []

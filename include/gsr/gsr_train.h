@@ -16,6 +16,12 @@
  *                             The reference has no loss code (its loop is a stub); the
  *                             definition is the upstream 3DGS one (11x11 Gaussian window,
  *                             sigma 1.5, zero padding, C1 = 0.01^2, C2 = 0.03^2, mean).
+ *   gsr_depth_loss         <- upstream 3DGS's depth regulariser (train.py: Ll1depth =
+ *                             depth_l1_weight(iteration) * mean |(invDepth - mono_invdepth) *
+ *                             depth_mask|) on the rasterizer's depth / alpha outputs
+ *                             (gsr_forward_aux of gsr.h), value and gradients in one pass.  The
+ *                             reference has no depth term; the normalised mode (depth / alpha)
+ *                             is this project's addition.
  *   gsr_adam_step          <- the six torch::optim::Adam instances of GaussianModel::setup
  *                             (src/scene/gaussian_model.cpp:323-345: default AdamOptions,
  *                             betas 0.9 / 0.999, eps 1e-8, no weight decay) stepped once each,
@@ -52,6 +58,26 @@ int gsr_loss_forward(const float* img, const float* gt, int32_t C, int32_t H, in
 /* dL/dimg (C x H x W) for dL/dloss = 1, from the maps the forward left in `maps`. */
 int gsr_loss_backward(const float* img, const float* gt, int32_t C, int32_t H, int32_t W,
                       float lambda_dssim, const void* maps, float* dL_dimg, void* stream);
+
+/* Depth L1 over an H x W plane (n = H * W pixels), for the depth / alpha outputs of
+ * gsr_forward_aux.  With m = mask[i] (1 when mask is NULL) and e = (pred - target) * m:
+ *   stats[0] = weight * mean_n |e|, stats[1] = mean_n |e|, stats[2] = the number of contributing
+ *   pixels (m != 0, and alpha >= alpha_min in normalised mode; exact up to 2^24).  The mean
+ *   divides by n, as upstream's .mean() does, not by the contributing count.
+ * Gradients for dL/dloss = 1, written for every pixel: dL/dpred = (weight / n) m sign(e), sign(0) = 0;
+ *   RAW         dL_ddepth = dL/dpred
+ *   NORMALIZED  dL_ddepth = dL/dpred / alpha, dL_dalpha = -dL/dpred depth / alpha^2; both 0 (and
+ *               the pixel contributes nothing) where alpha < alpha_min.
+ * alpha / dL_dalpha: required in NORMALIZED mode, ignored (may be NULL) in RAW mode.  alpha_min
+ * > 0 in NORMALIZED mode; weight finite and >= 0.  Planes: any 4-byte-aligned pointer (float4
+ * accesses when all are 16-byte aligned).  scratch: gsr_depth_loss_scratch_bytes(H, W) bytes,
+ * 8-byte aligned.  One pass plus a one-block finalize; deterministic (fixed-order sums, no atomics). */
+#define GSR_DEPTH_RAW 0         /* pred = depth           (upstream: the un-normalised blend)   */
+#define GSR_DEPTH_NORMALIZED 1  /* pred = depth / alpha   where alpha >= alpha_min; other pixels contribute nothing */
+size_t gsr_depth_loss_scratch_bytes(int32_t H, int32_t W);
+int gsr_depth_loss(const float* depth, const float* alpha, const float* target, const float* mask,
+                   int32_t H, int32_t W, float weight, int32_t mode, float alpha_min,
+                   void* scratch, float* stats, float* dL_ddepth, float* dL_dalpha, void* stream);
 
 /* Activation applied by the getter in front of a parameter group (its gradient arrives with
  * respect to the activated value; gsr_adam_step converts it to the raw leaf first). */
