@@ -239,10 +239,28 @@ uint32_t expected_layout(long long n, int gx, int gy, long long cap) {
     return w;
 }
 
+// The backward must run with the forward's GSR_FLAG_ANTIALIAS choice (gsr.h).
+int check_antialias(const gsr_raster_settings* rs, const gsr_buffers* b) {
+    const bool flag = (rs->flags & GSR_FLAG_ANTIALIAS) != 0, bit = (b->layout & kBufAntialias) != 0;
+    if (flag != bit)
+        return fail(GSR_ERR_LAYOUT, "GSR_FLAG_ANTIALIAS is %s but the forward ran %s it (gsr_buffers.layout = 0x%08x)",
+                    flag ? "set" : "clear", flag ? "without" : "with", b->layout);
+    return 0;
+}
+
+// The multi-GPU calls render without the opacity compensation only.
+int refuse_antialias(const gsr_raster_settings* rs, const char* who) {
+    if (rs->flags & GSR_FLAG_ANTIALIAS)
+        return fail(-1, "%s: GSR_FLAG_ANTIALIAS is not supported by the shard / band calls", who);
+    return 0;
+}
+
 // Every use of a forward's buffers after the forward checks the layout word: missing tag (a
 // struct rebuilt without the field) or bits that disagree with what the forward of these sizes
 // chose would make the backward read the wrong arrays -- refused instead (ABI 4).
-int check_layout(const gsr_camera* cam, int ty0, int ty1, const gsr_buffers* b) {
+// rs: the call's settings -- GSR_FLAG_ANTIALIAS must be what the forward ran with (the records then
+// carry o', and B2 owes the chain through the compensation); nullptr: an accessor, no flag to compare.
+int check_layout(const gsr_camera* cam, int ty0, int ty1, const gsr_buffers* b, const gsr_raster_settings* rs) {
     if ((b->layout & GSR_LAYOUT_TAG_MASK) != GSR_LAYOUT_TAG)
         return fail(GSR_ERR_LAYOUT,
                     "gsr_buffers.layout = 0x%08x is not a forward's (ABI %d): pass the forward's gsr_buffers "
@@ -252,12 +270,14 @@ int check_layout(const gsr_camera* cam, int ty0, int ty1, const gsr_buffers* b) 
     const uint32_t want = expected_layout(b->n_local, gx, gy, b->capacity);
     // the aux bits say which forward sized the buffers; aux buffers hold the plain arrays at the
     // plain offsets, so every plain use accepts them (gsr_backward_aux asks for the bits itself)
-    if ((b->layout & ~(kBufAux | kBufInvDepth)) != want || (b->layout & (kBufAux | kBufInvDepth)) == kBufInvDepth)
+    // (likewise the anti-alias bit: it changes the records' values, not the arrays)
+    if ((b->layout & ~(kBufAux | kBufInvDepth | kBufAntialias)) != want ||
+        (b->layout & (kBufAux | kBufInvDepth)) == kBufInvDepth)
         return fail(GSR_ERR_LAYOUT,
                     "gsr_buffers.layout = 0x%08x disagrees with the buffers (0x%08x for %d entries, capacity %d, "
                     "tile rows [%d, %d) of %d x %d)",
                     b->layout, want, b->n_local, b->capacity, ty0, ty1, gx, gy);
-    return 0;
+    return rs ? check_antialias(rs, b) : 0;
 }
 
 Views views(const gsr_camera* cam, long long n, const gsr_buffers* b) {
@@ -343,8 +363,11 @@ struct FwdJob {
     int vgy = 0, vh = 0;  // views mode: tile rows per view band, pixel rows per view (0: one image)
     bool rows_counted = false;  // F1 wrote the row-bucketed binning's pass-A counts (run_preprocess)
     const gsr_aux_out* aux = nullptr;  // gsr_forward_aux: the depth / alpha outputs (full image)
-    uint32_t aux_bits() const {
-        return aux ? kBufAux | ((rs->flags & GSR_FLAG_INVDEPTH) ? kBufInvDepth : 0u) : 0u;
+    bool antialias() const { return (rs->flags & GSR_FLAG_ANTIALIAS) != 0; }
+    // the layout bits that say how the forward ran (the rest say which arrays the binning chose)
+    uint32_t mode_bits() const {
+        return (aux ? kBufAux | ((rs->flags & GSR_FLAG_INVDEPTH) ? kBufInvDepth : 0u) : 0u) |
+               (antialias() ? kBufAntialias : 0u);
     }
 };
 
@@ -362,7 +385,7 @@ int fwd_phase1(FwdJob& j, gsr_alloc_fn alloc_geom, gsr_alloc_fn alloc_image, voi
     j.gy = div_up(H, kTile);
     band(cam, rs, &j.ty0, &j.ty1);
     std::memset(bufs, 0, sizeof *bufs);
-    bufs->layout = GSR_LAYOUT_TAG | (use_presort(j.n, j.gx, j.gy) ? kBufPresort : 0u) | j.aux_bits();
+    bufs->layout = GSR_LAYOUT_TAG | (use_presort(j.n, j.gx, j.gy) ? kBufPresort : 0u) | j.mode_bits();
     bufs->num_rendered = -1;
     bufs->n_local = (int32_t)j.n;
     bufs->geom = alloc_geom(ctx, GeomLayout(j.n).total);
@@ -413,7 +436,7 @@ int fwd_phase2(FwdJob& j, long long cap, gsr_alloc_fn alloc_binning, void* ctx, 
     // per-tile depth order sorts them by the whole (depth, gid) key); recorded in the buffers so
     // that every later view of them (backward, accessors) finds the same arrays.
     const bool scanned = use_rb_binning(j.n, j.gx, j.gy);  // phase 1 ran the three-kernel scan
-    bufs->layout = expected_layout(j.n, j.gx, j.gy, cap) | j.aux_bits();
+    bufs->layout = expected_layout(j.n, j.gx, j.gy, cap) | j.mode_bits();
     const Views v = views(cam, j.n, bufs);
     auto depth_sort = [&](bool unordered, const uint2* src) {
         return launch_tile_depth_sort(v.ranges, j.ty0 * j.gx, ntiles, cap, v.depth_key, v.sorted_gid, v.ovf,
@@ -525,7 +548,9 @@ int run_preprocess(const FwdJob& j, const gsr_gaussians* gs, int32_t* radii, con
         po.rb_hist = v.rb_histA;
         po.bsum = v.lookback + 16;  // the F2 scan's block partials (the lookback words are unused here)
     }
-    GSR_STAGE(GSR_STAGE_PREPROCESS, launch_preprocess(*cam, gauss_in(gs), j.ty0, j.ty1, po, stream), "preprocess");
+    GSR_STAGE(GSR_STAGE_PREPROCESS, launch_preprocess(*cam, gauss_in(gs), j.ty0, j.ty1, po, stream,
+                                                      j.antialias()),
+              "preprocess");
     return 0;
 }
 
@@ -539,7 +564,7 @@ int blend_backward(const gsr_camera* cam, const gsr_raster_settings* rs, const g
     if (n <= 0) return 0;
     int ty0, ty1;
     band(cam, rs, &ty0, &ty1);
-    if (int e = check_layout(cam, ty0, ty1, bufs)) return e;
+    if (int e = check_layout(cam, ty0, ty1, bufs, rs)) return e;
     const Views v = views(cam, n, bufs);
     if (!alloc_scratch) return fail(-1, "null scratch allocator");
     // aux: gsr_backward_aux (full image, aux buffers: checked by the caller)
@@ -809,7 +834,8 @@ int gsr_forward_views(int32_t V, const gsr_camera* cams, const gsr_gaussians* gs
     if (int e = fwd_phase1(j, alloc_geom, alloc_image, ctx, stream, debug, false, [&](const Views& v) {
             if (gs->P <= 0) return 0;
             PreOut po{radii, v.depth_key, v.tiles, v.rec, v.rect, v.flags, v.counters};
-            GSR_STAGE(GSR_STAGE_PREPROCESS, launch_preprocess_views(cams, V, gauss_in(gs), po, stream),
+            GSR_STAGE(GSR_STAGE_PREPROCESS, launch_preprocess_views(cams, V, gauss_in(gs), po, stream,
+                                                                    j.antialias()),
                       "preprocess (views)");
             if (exact) GSR_CHECK_HIP(begin_read(v.counters, 2 * kCountSlots, stream), "read counts");
             return 0;
@@ -829,7 +855,7 @@ int gsr_backward_views(int32_t V, const gsr_camera* cams, const gsr_gaussians* g
     if (int e = check_grads(gs, grads)) return e;
     const long long n = (long long)V * gs->P;
     if (!bufs || bufs->n_local != n) return fail(-1, "forward buffers do not match V * P view entries");
-    if (int e = check_layout(&tall, 0, div_up(tall.height, kTile), bufs)) return e;
+    if (int e = check_layout(&tall, 0, div_up(tall.height, kTile), bufs, rs)) return e;
     hipStream_t stream = (hipStream_t)stream_;
     const bool debug = (rs->flags & GSR_FLAG_DEBUG) != 0;
     gsr_raster_settings rv = *rs;
@@ -863,7 +889,8 @@ int gsr_backward_views(int32_t V, const gsr_camera* cams, const gsr_gaussians* g
     }
     const Views v = views(&tall, n, bufs);
     GSR_STAGE(GSR_STAGE_PREPROCESS_BWD, launch_preprocess_backward_views(cams, V, in, v.depth_key, v.flags, grad2d, out,
-                                                                         scratch, stream),
+                                                                         scratch, stream,
+                                                                         (rs->flags & GSR_FLAG_ANTIALIAS) != 0),
               "preprocess backward (views)");
     if (V > 1) GSR_STAGE(GSR_STAGE_PREPROCESS_BWD, launch_views_sum(in, V, out, scratch, stream), "views sum");
     return 0;
@@ -879,7 +906,7 @@ static int backward_one(const gsr_camera* cam, const gsr_gaussians* gs, const gs
     {
         int ty0, ty1;
         band(cam, rs, &ty0, &ty1);
-        if (int e = check_layout(cam, ty0, ty1, bufs)) return e;  // before any allocation
+        if (int e = check_layout(cam, ty0, ty1, bufs, rs)) return e;  // before any allocation
     }
     const bool inv = (rs->flags & GSR_FLAG_INVDEPTH) != 0;
     if (aux && !(bufs->layout & kBufAux))
@@ -898,7 +925,8 @@ static int backward_one(const gsr_camera* cam, const gsr_gaussians* gs, const gs
     // a full image's stored SH clamp bits; aux: grad2d slot 9 is dL/dz (1) or dL/d(1/z) (2)
     GSR_STAGE(GSR_STAGE_PREPROCESS_BWD, launch_preprocess_backward(*cam, gauss_in(gs), 0, gs->P, v.depth_key,
                                                                    stored_flags(cam, rs, v.flags), grad2d,
-                                                                   grad_out(grads), stream, aux ? (inv ? 2 : 1) : 0),
+                                                                   grad_out(grads), stream, aux ? (inv ? 2 : 1) : 0,
+                                                                   (rs->flags & GSR_FLAG_ANTIALIAS) != 0),
               aux ? "preprocess backward (aux)" : "preprocess backward");
     return 0;
 }
@@ -941,13 +969,15 @@ int gsr_backward_preprocess(const gsr_camera* cam, const gsr_gaussians* gs, cons
     if (gs->P == 0) return 0;
     if (int e = check_grads(gs, grads)) return e;
     if (!bufs || !bufs->geom || !grad2d) return fail(-1, "missing forward buffers / grad2d");
+    if (int e = check_antialias(rs, bufs)) return e;
     hipStream_t stream = (hipStream_t)stream_;
     const bool debug = (rs->flags & GSR_FLAG_DEBUG) != 0;
     const GeomLayout gl(gs->P);
     GSR_STAGE(GSR_STAGE_PREPROCESS_BWD, launch_preprocess_backward(*cam, gauss_in(gs), 0, gs->P,
                                                                    at<uint32_t>(bufs->geom, gl.depth_key),
                                                                    stored_flags(cam, rs, at<uint32_t>(bufs->geom, gl.flags)),
-                                                                   grad2d, grad_out(grads), stream),
+                                                                   grad2d, grad_out(grads), stream, 0,
+                                                                   (rs->flags & GSR_FLAG_ANTIALIAS) != 0),
               "preprocess backward");
     return 0;
 }
@@ -958,6 +988,7 @@ int gsr_shard_forward(const gsr_camera* cam, const gsr_gaussians* gs, const gsr_
                       uint32_t* row_hist, void* stream_) {
     g_err.clear();
     if (int e = validate(cam, gs, rs)) return e;
+    if (int e = refuse_antialias(rs, "gsr_shard_forward")) return e;
     if (pair_cap < 0 || !send || !shard_state || (gs->P > 0 && !radii)) return fail(-1, "shard: null buffer / bad pair_cap");
     const int gy = div_up(cam->height, kTile);
     if (row_hist && gy > kMaxHistRows) return fail(-1, "shard: row histogram holds at most %d tile rows", kMaxHistRows);
@@ -990,6 +1021,7 @@ int gsr_band_forward(const gsr_camera* cam, const gsr_raster_settings* rs, int32
                      gsr_alloc_fn alloc_image, void* ctx, gsr_buffers* bufs, void* stream_) {
     g_err.clear();
     if (!cam || !rs) return fail(-1, "null camera / settings");
+    if (int e = refuse_antialias(rs, "gsr_band_forward")) return e;
     if (nsrc < 1 || nsrc > kMaxBands || pair_cap < 0) return fail(-1, "band: bad nsrc / pair_cap");
     if (!recv || !out_color || !bufs || !alloc_geom || !alloc_binning || !alloc_image)
         return fail(-1, "band: null buffer / allocator");
@@ -1019,6 +1051,7 @@ int gsr_band_backward(const gsr_camera* cam, const gsr_raster_settings* rs, int3
                       void* grad_send, void* stream_) {
     g_err.clear();
     if (!cam || !rs || !bufs || !grad_send) return fail(-1, "band backward: null argument");
+    if (int e = refuse_antialias(rs, "gsr_band_backward")) return e;
     if ((long long)nsrc * pair_cap != bufs->n_local) return fail(-1, "band backward: nsrc * pair_cap != the forward's");
     const bool debug = (rs->flags & GSR_FLAG_DEBUG) != 0;
     return blend_backward(cam, rs, bufs, dL_dpix, alloc_scratch, ctx, static_cast<float*>(grad_send),
@@ -1030,6 +1063,7 @@ int gsr_shard_backward(const gsr_camera* cam, const gsr_gaussians* gs, const gsr
                        const gsr_grads* grads, void* stream_) {
     g_err.clear();
     if (int e = validate(cam, gs, rs)) return e;
+    if (int e = refuse_antialias(rs, "gsr_shard_backward")) return e;
     if (gs->P == 0) return 0;
     if (int e = check_grads(gs, grads)) return e;
     if (!shard_state || !grad_recv || pair_cap < 0) return fail(-1, "shard backward: null buffer / bad pair_cap");
@@ -1057,6 +1091,7 @@ int gsr_band_publish(const gsr_camera* cam, const gsr_raster_settings* rs, int32
                      int64_t status_off, void* stream_) {
     g_err.clear();
     if (!cam || !rs || !out_color || !send || !bufs || !bufs->image || !row) return fail(-1, "publish: null argument");
+    if (int e = refuse_antialias(rs, "gsr_band_publish")) return e;
     if (cam->width <= 0 || cam->height <= 0) return fail(-1, "publish: bad image size");
     if (nbands < 1 || nbands > kMaxBands || pair_cap < 0) return fail(-1, "publish: bad nbands / pair_cap");
     int ty0, ty1;

@@ -92,6 +92,7 @@ constexpr long long kRbMaxCap = 1LL << 30;  // the look-back's 30-bit counts (rb
 constexpr uint32_t kBufRowBucketed = GSR_LAYOUT_ROW_BUCKETED;
 constexpr uint32_t kBufPresort = GSR_LAYOUT_PRESORT;
 constexpr uint32_t kBufAux = GSR_LAYOUT_AUX, kBufInvDepth = GSR_LAYOUT_INVDEPTH;  // gsr_forward_aux
+constexpr uint32_t kBufAntialias = GSR_LAYOUT_ANTIALIAS;                          // GSR_FLAG_ANTIALIAS
 // the pre-sort's buffers (GeomLayout: sized from n alone) / the pre-sort itself for an image of
 // gx x gy tiles
 inline bool presort_possible(long long n) { return n >= kPresortMin; }

@@ -31,8 +31,10 @@ struct PreOut {
 // F1: projection, EWA cov2D, conic, radius, tile rect (clipped to the tile rows [ty0, ty1)),
 // SH->RGB (bit-exact vs the oracle).  A Gaussian shard is `in` with every pointer advanced to
 // its first Gaussian and P = its length (outputs are indexed by the shard-local index).
+// aa (GSR_FLAG_ANTIALIAS): the record carries o' = o sqrt(max(0.000025, det(cov2D) / det(cov2D + 0.3 I)))
+// (its o, its log2 o, its footprint extents); every other output is bit for bit the plain one.
 int launch_preprocess(const gsr_camera& cam, const GaussIn& in, int ty0, int ty1, const PreOut& out,
-                      hipStream_t s);
+                      hipStream_t s, bool aa = false);
 // Cameras by value in the kernel arguments: one, or up to kMaxViews (views mode, grid.y = view).
 template <int NV>
 struct CamArg {
@@ -40,7 +42,8 @@ struct CamArg {
 };
 // Views mode (gsr_forward_views): V <= kMaxViews views of the same size, one launch (grid.y =
 // view); view v's outputs at entries v * P + g, its tiles / pixel rows offset into a tall image.
-int launch_preprocess_views(const gsr_camera* cams, int V, const GaussIn& in, const PreOut& out, hipStream_t s);
+int launch_preprocess_views(const gsr_camera* cams, int V, const GaussIn& in, const PreOut& out, hipStream_t s,
+                            bool aa = false);
 
 // ---- gsr_radix.hip ----
 // LSD radix sort of (u32 key, u32 value) by key bits [0, nbits); vals_in == nullptr means the
@@ -182,7 +185,9 @@ struct GradOut {
 // floats each).  Inputs are indexed by g; grad2d and all outputs by g - g0.
 int launch_preprocess_backward(const gsr_camera& cam, const GaussIn& in, int g0, int g1,
                                const uint32_t* depth_key, const uint32_t* flags, const float* grad2d,
-                               const GradOut& out, hipStream_t s, int aux = 0);
+                               const GradOut& out, hipStream_t s, int aux = 0, bool aa = false);
+// (aa: the forward ran with GSR_FLAG_ANTIALIAS -- grad2d slot 5 is dL/do'; the chain through the
+// compensation reaches the opacity and the cov2D gradients)
 // (aux: 0 = colour only; 1 = grad2d slot 9 is dL/dz of the depth channel, added to the view-space
 // z gradient; 2 = it is dL/d(1/z), scaled by -1/z^2 first)
 // Views mode: B2 of V views in one launch (grid.y = view) from the per-(view, Gaussian) entries
@@ -191,7 +196,7 @@ int launch_preprocess_backward(const gsr_camera& cam, const GaussIn& in, int g0,
 // slice), which launch_views_sum then adds to `out` in view order.
 int launch_preprocess_backward_views(const gsr_camera* cams, int V, const GaussIn& in, const uint32_t* depth_key,
                                      const uint32_t* flags, const float* grad2d, const GradOut& out,
-                                     const GradOut& scratch, hipStream_t s);
+                                     const GradOut& scratch, hipStream_t s, bool aa = false);
 int launch_views_sum(const GaussIn& in, int V, const GradOut& out, const GradOut& scratch, hipStream_t s);
 
 // ---- multi-GPU exchange (gsr_shard.hip) ----

@@ -36,6 +36,7 @@ __device__ inline int imax(int a, int b) { return a > b ? a : b; }
 // tiles_touched and what the blend record needs.
 struct Geo {
     float xs, ys, cA, cB, cC, a, c;
+    float coef;  // AA only: the opacity compensation sqrt(max(0.000025, det(cov2D) / det(cov2D + 0.3 I)))
     int minx, miny, maxx, maxy;
     int32_t radius;
     uint32_t key, tiles;
@@ -75,6 +76,9 @@ __device__ __forceinline__ Params load_params(const GaussIn& in, int g) {
     return P;
 }
 
+// AA (GSR_FLAG_ANTIALIAS): also G.coef, from the covariance before and after the 0.3 px^2 dilation;
+// nothing else changes, so radius, rect, tiles and depth key are those of the plain form.
+template <bool AA>
 __device__ __forceinline__ Geo preprocess_geom(const gsr_camera& cam, const GaussIn& in, const Params& I, int grid_x,
                                                int grid_y, int ty0, int ty1) {
     const float* V = cam.viewmatrix;
@@ -154,11 +158,13 @@ __device__ __forceinline__ Geo preprocess_geom(const gsr_camera& cam, const Gaus
             U0[j] = T0[0] * S[0 + j] + T0[1] * S[3 + j] + T0[2] * S[6 + j];
             U1[j] = T1[0] * S[0 + j] + T1[1] * S[3 + j] + T1[2] * S[6 + j];
         }
-        const float a = (U0[0] * T0[0] + U0[1] * T0[1] + U0[2] * T0[2]) + 0.3f;
+        const float a0 = U0[0] * T0[0] + U0[1] * T0[1] + U0[2] * T0[2];
         const float b = U0[0] * T1[0] + U0[1] * T1[1] + U0[2] * T1[2];
-        const float c = (U1[0] * T1[0] + U1[1] * T1[1] + U1[2] * T1[2]) + 0.3f;
+        const float c0 = U1[0] * T1[0] + U1[1] * T1[1] + U1[2] * T1[2];
+        const float a = a0 + 0.3f, c = c0 + 0.3f;
         const float det = a * c - b * b;
         if (det != 0.0f) {
+            if (AA) G.coef = sqrtf(fmaxf(0.000025f, (a0 * c0 - b * b) / det));
             const float det_inv = 1.0f / det;
             const float cA = c * det_inv, cB = -b * det_inv, cC = a * det_inv;
             const float mid = 0.5f * (a + c);
@@ -273,7 +279,7 @@ constexpr int kChunkF = 3 * kChunkK;     // floats per row per chunk
 // NV > 1 (gsr_forward_views): view v = blockIdx.y projects the same Gaussians with cams.c[v]; its
 // outputs go to entry e = v * P + g and its tile rows are offset by v * grid_y -- the views are
 // consecutive bands of tile rows of one tall image for every later stage.
-template <int SH, int NV>
+template <int SH, int NV, bool AA = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void preprocess_kernel(const CamArg<NV> cams,
                                                          const GaussIn in,
                                                          int grid_x, int grid_y, int ty0, int ty1,
@@ -329,7 +335,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void p
     Geo G{};
     G.key = 0xFFFFFFFFu;
     if (g < in.P) {
-        G = preprocess_geom(cam, in, I, grid_x, grid_y, ty0, ty1);
+        G = preprocess_geom<AA>(cam, in, I, grid_x, grid_y, ty0, ty1);
+        if (AA) I.opac = I.opac * G.coef;  // o' from here on: no register lives longer than in the plain form
         if (NV > 1) {  // view v's band of tile rows in the tall image (the record stays in the
             G.miny += view * grid_y;  // view's own pixel coordinates: F6 / B1 take pixel y
             G.maxy += view * grid_y;  // relative to the view's band, so every value is bit-equal
@@ -446,37 +453,44 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void p
 
 }  // namespace
 
-template <int NV>
+template <int NV, bool AA>
 static void launch_preprocess_nv(const CamArg<NV>& cams, int V, const GaussIn& in, int ty0, int ty1,
                                  const PreOut& out, hipStream_t s) {
     const int gx = div_up(cams.c[0].width, kTile), gy = div_up(cams.c[0].height, kTile);
     const bool sh = in.sh_rest && !in.colors && in.D > 0;
     const dim3 grid(div_up(in.P, 256), V), block(256);
     if (sh && in.M_rest * 3 <= 48 && (reinterpret_cast<uintptr_t>(in.sh_rest) & 15) == 0)
-        hipLaunchKernelGGL((preprocess_kernel<kShGlds, NV>), grid, block,
+        hipLaunchKernelGGL((preprocess_kernel<kShGlds, NV, AA>), grid, block,
                            4 * 1024 * ((64 * in.M_rest * 3 * 4 + 1023) / 1024), s, cams, in, gx, gy, ty0, ty1, out);
     else if (sh)
-        hipLaunchKernelGGL((preprocess_kernel<kShChunks, NV>), grid, block, sizeof(float) * 256 * kChunkF, s, cams, in,
+        hipLaunchKernelGGL((preprocess_kernel<kShChunks, NV, AA>), grid, block, sizeof(float) * 256 * kChunkF, s, cams, in,
                            gx, gy, ty0, ty1, out);
     else
-        hipLaunchKernelGGL((preprocess_kernel<kShDirect, NV>), grid, block, 0, s, cams, in, gx, gy, ty0, ty1, out);
+        hipLaunchKernelGGL((preprocess_kernel<kShDirect, NV, AA>), grid, block, 0, s, cams, in, gx, gy, ty0, ty1, out);
 }
 
 int launch_preprocess(const gsr_camera& cam, const GaussIn& in, int ty0, int ty1, const PreOut& out,
-                      hipStream_t s) {
+                      hipStream_t s, bool aa) {
     if (in.P <= 0) return 0;
     CamArg<1> c1{{cam}};
-    launch_preprocess_nv(c1, 1, in, ty0, ty1, out, s);
+    if (aa)
+        launch_preprocess_nv<1, true>(c1, 1, in, ty0, ty1, out, s);
+    else
+        launch_preprocess_nv<1, false>(c1, 1, in, ty0, ty1, out, s);
     return (int)hipGetLastError();
 }
 
-int launch_preprocess_views(const gsr_camera* cams, int V, const GaussIn& in, const PreOut& out, hipStream_t s) {
+int launch_preprocess_views(const gsr_camera* cams, int V, const GaussIn& in, const PreOut& out, hipStream_t s,
+                            bool aa) {
     if (in.P <= 0 || V <= 0) return 0;
     if (V > kMaxViews) return -1;
     CamArg<kMaxViews> cv{};
     for (int v = 0; v < V; ++v) cv.c[v] = cams[v];
     const int gy = div_up(cams[0].height, kTile);
-    launch_preprocess_nv(cv, V, in, 0, gy, out, s);
+    if (aa)
+        launch_preprocess_nv<kMaxViews, true>(cv, V, in, 0, gy, out, s);
+    else
+        launch_preprocess_nv<kMaxViews, false>(cv, V, in, 0, gy, out, s);
     return (int)hipGetLastError();
 }
 

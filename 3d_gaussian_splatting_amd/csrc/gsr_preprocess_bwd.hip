@@ -230,10 +230,14 @@ __device__ __forceinline__ BwdIn load_bwd_in(const GaussIn& in, int g, int o, co
 // One Gaussian's chain rule.  `lrest`: this thread's SH-rest row staged in LDS (read, then
 // overwritten in place with the row's gradient), or nullptr when there is no SH-rest input.
 // AUX: 0 = colour only; 1 = bi.gz is dL/dz of the depth channel; 2 = dL/d(1/z).
-template <int AUX>
+// AA (GSR_FLAG_ANTIALIAS): the forward blended o' = o coef, coef = sqrt(max(0.000025, r)), r = det0 / det
+// with det0 the determinant before the 0.3 px^2 dilation: g2[5] is dL/do', so dL/do = coef dL/do' and
+// dL/dr = o dL/do' / (2 coef) (zero at the clamp) joins the cov2D gradients.  opac_in: the input opacity o
+// (AA only; loaded with the other per-Gaussian inputs).
+template <int AUX, bool AA>
 __device__ __forceinline__ void preprocess_backward_one(const gsr_camera& cam, const GaussIn& in, int g, int o,
                                                         const BwdIn& bi, const uint32_t* __restrict__ flags,
-                                                        const GradOut& out, float* lrest) {
+                                                        const GradOut& out, float* lrest, float opac_in) {
     const bool visible = bi.visible;
     // ---- 2D gradients ----
     float g2[9];
@@ -247,7 +251,7 @@ __device__ __forceinline__ void preprocess_backward_one(const gsr_camera& cam, c
         out.conic[3 * o + 1] = g2[3];
         out.conic[3 * o + 2] = g2[4];
     }
-    out.opac[o] = g2[5];
+    if (!AA || !visible) out.opac[o] = g2[5];
 
     const float* V = cam.viewmatrix;
     const float* Pm = cam.projmatrix;
@@ -449,15 +453,28 @@ __device__ __forceinline__ void preprocess_backward_one(const gsr_camera& cam, c
         ST0[i] = S[3 * i + 0] * T0[0] + S[3 * i + 1] * T0[1] + S[3 * i + 2] * T0[2];
         ST1[i] = S[3 * i + 0] * T1[0] + S[3 * i + 1] * T1[1] + S[3 * i + 2] * T1[2];
     }
-    const float a = (ST0[0] * T0[0] + ST0[1] * T0[1] + ST0[2] * T0[2]) + 0.3f;
+    const float a0 = ST0[0] * T0[0] + ST0[1] * T0[1] + ST0[2] * T0[2];  // cov2D before the dilation
+    const float a = a0 + 0.3f;
     const float b = ST0[0] * T1[0] + ST0[1] * T1[1] + ST0[2] * T1[2];
-    const float c = (ST1[0] * T1[0] + ST1[1] * T1[1] + ST1[2] * T1[2]) + 0.3f;
+    const float c0 = ST1[0] * T1[0] + ST1[1] * T1[1] + ST1[2] * T1[2];
+    const float c = c0 + 0.3f;
     const float det = a * c - b * b;
     const float dA = g2[2], dB = g2[3], dC = g2[4];
     const float inv2 = 1.0f / (det * det);
-    const float dL_da = inv2 * (-c * c * dA + b * c * dB - b * b * dC);
-    const float dL_db = inv2 * (2.f * b * c * dA - (a * c + b * b) * dB + 2.f * a * b * dC);
-    const float dL_dc = inv2 * (-b * b * dA + a * b * dB - a * a * dC);
+    float dL_da = inv2 * (-c * c * dA + b * c * dB - b * b * dC);
+    float dL_db = inv2 * (2.f * b * c * dA - (a * c + b * b) * dB + 2.f * a * b * dC);
+    float dL_dc = inv2 * (-b * b * dA + a * b * dB - a * a * dC);
+    if constexpr (AA) {
+        // r's derivatives in their cancellation-free forms: (c0 det - det0 c) / det^2 = (h (c0^2 + b^2) + h^2 c0) / det^2
+        const float h = 0.3f;
+        const float r = (a0 * c0 - b * b) / det;
+        const float coef = sqrtf(fmaxf(0.000025f, r));
+        out.opac[o] = coef * g2[5];
+        const float dL_dr = r <= 0.000025f ? 0.f : (opac_in * g2[5]) / (2.f * coef);
+        dL_da += dL_dr * ((h * (c0 * c0 + b * b) + h * h * c0) * inv2);
+        dL_dc += dL_dr * ((h * (a0 * a0 + b * b) + h * h * a0) * inv2);
+        dL_db += dL_dr * (-2.f * b * (h * (a0 + c0) + h * h) * inv2);
+    }
     float dS[6];
     dS[0] = T0[0] * T0[0] * dL_da + T0[0] * T1[0] * dL_db + T1[0] * T1[0] * dL_dc;
     dS[3] = T0[1] * T0[1] * dL_da + T0[1] * T1[1] * dL_db + T1[1] * T1[1] * dL_dc;
@@ -541,7 +558,7 @@ __device__ __forceinline__ GradOut view_out(const GradOut& out, const GradOut& s
 }
 
 // SUM: the 2D gradients are the shard's band returns (BandSum), summed here (g0 = 0).
-template <int NV, bool SUM, int AUX = 0>
+template <int NV, bool SUM, int AUX = 0, bool AA = false>
 __global__ __launch_bounds__(256) void preprocess_backward_kernel(
     const CamArg<NV> cams, const GaussIn in, int g0, int n, const uint32_t* __restrict__ depth_key,
     const uint32_t* __restrict__ flags, const float* __restrict__ grad2d, GradOut out, const GradOut scratch,
@@ -582,6 +599,8 @@ __global__ __launch_bounds__(256) void preprocess_backward_kernel(
     }
     BwdIn bi{};
     if (o < n) bi = load_bwd_in<SUM>(in, g0 + o, o, depth_key, flags, grad2d, bs);
+    float opac_in = 0.f;
+    if (AA && o < n) opac_in = in.opac[g0 + o];
     if (stage) {  // coalesced staging of the block's SH-rest rows (see preprocess_kernel)
         if (v4) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's pieces have landed
@@ -592,7 +611,8 @@ __global__ __launch_bounds__(256) void preprocess_backward_kernel(
         __syncthreads();
     }
     if (o < n)
-        preprocess_backward_one<AUX>(cam, in, g0 + o, o, bi, flags, out, stage ? sh_lds + threadIdx.x * M3 : nullptr);
+        preprocess_backward_one<AUX, AA>(cam, in, g0 + o, o, bi, flags, out, stage ? sh_lds + threadIdx.x * M3 : nullptr,
+                                         opac_in);
     if (stage) {  // coalesced write-back of the SH-rest gradient rows
         __syncthreads();
         const int nf = rows * M3;
@@ -628,12 +648,21 @@ int launch_gather_grad2d(const uint32_t* offsets, const float* partial, const fl
 
 int launch_preprocess_backward(const gsr_camera& cam, const GaussIn& in, int g0, int g1,
                                const uint32_t* depth_key, const uint32_t* flags, const float* grad2d,
-                               const GradOut& out, hipStream_t s, int aux) {
+                               const GradOut& out, hipStream_t s, int aux, bool aa) {
     const int n = g1 - g0;
     if (n <= 0) return 0;
     const size_t lds = (in.sh_rest && !in.colors) ? sizeof(float) * 256 * 3 * in.M_rest : 0;
     const CamArg<1> c1{{cam}};
-    if (aux == 1)
+    if (aa && aux == 1)
+        hipLaunchKernelGGL((preprocess_backward_kernel<1, false, 1, true>), dim3(div_up(n, 256)), dim3(256), lds, s, c1,
+                           in, g0, n, depth_key, flags, grad2d, out, GradOut{}, BandSum{});
+    else if (aa && aux == 2)
+        hipLaunchKernelGGL((preprocess_backward_kernel<1, false, 2, true>), dim3(div_up(n, 256)), dim3(256), lds, s, c1,
+                           in, g0, n, depth_key, flags, grad2d, out, GradOut{}, BandSum{});
+    else if (aa)
+        hipLaunchKernelGGL((preprocess_backward_kernel<1, false, 0, true>), dim3(div_up(n, 256)), dim3(256), lds, s, c1,
+                           in, g0, n, depth_key, flags, grad2d, out, GradOut{}, BandSum{});
+    else if (aux == 1)
         hipLaunchKernelGGL((preprocess_backward_kernel<1, false, 1>), dim3(div_up(n, 256)), dim3(256), lds, s, c1, in,
                            g0, n, depth_key, flags, grad2d, out, GradOut{}, BandSum{});
     else if (aux == 2)
@@ -657,13 +686,17 @@ int launch_preprocess_backward_banded(const gsr_camera& cam, const GaussIn& in, 
 
 int launch_preprocess_backward_views(const gsr_camera* cams, int V, const GaussIn& in, const uint32_t* depth_key,
                                      const uint32_t* flags, const float* grad2d, const GradOut& out,
-                                     const GradOut& scratch, hipStream_t s) {
+                                     const GradOut& scratch, hipStream_t s, bool aa) {
     if (in.P <= 0 || V <= 0) return 0;
     if (V > kMaxViews) return -1;
     CamArg<kMaxViews> cv{};
     for (int v = 0; v < V; ++v) cv.c[v] = cams[v];
     const size_t lds = (in.sh_rest && !in.colors) ? sizeof(float) * 256 * 3 * in.M_rest : 0;
-    hipLaunchKernelGGL((preprocess_backward_kernel<kMaxViews, false>), dim3(div_up(in.P, 256), V), dim3(256), lds, s,
+    if (aa)
+        hipLaunchKernelGGL((preprocess_backward_kernel<kMaxViews, false, 0, true>), dim3(div_up(in.P, 256), V),
+                           dim3(256), lds, s, cv, in, 0, in.P, depth_key, flags, grad2d, out, scratch, BandSum{});
+    else
+        hipLaunchKernelGGL((preprocess_backward_kernel<kMaxViews, false>), dim3(div_up(in.P, 256), V), dim3(256), lds, s,
                        cv, in, 0, in.P, depth_key, flags, grad2d, out, scratch, BandSum{});
     return (int)hipGetLastError();
 }

@@ -26,8 +26,9 @@ static gsr::RasterCamera cam_from_py(int w, int h, float tx, float ty, const std
 }
 
 static gsr::RasterSettings settings_from_py(const std::vector<float>& bg, float smod, int D, int ty0, int ty1,
-                                            bool debug, int max_rendered) {
+                                            bool debug, int max_rendered, bool antialiasing) {
     gsr::RasterSettings rs;
+    rs.antialiasing = antialiasing;
     rs.max_rendered = max_rendered;
     for (int i = 0; i < 3; ++i) rs.bg[i] = bg.at(i);
     rs.scale_modifier = smod;
@@ -179,7 +180,8 @@ PYBIND11_MODULE(_gsr_torch, m) {
     py::class_<gsr::RasterSettings>(m, "RasterSettings")
         .def(py::init(&settings_from_py), py::arg("bg"), py::arg("scale_modifier") = 1.0f,
              py::arg("sh_degree") = 0, py::arg("tile_y0") = 0, py::arg("tile_y1") = INT32_MAX,
-             py::arg("debug") = false, py::arg("max_rendered") = 0);
+             py::arg("debug") = false, py::arg("max_rendered") = 0, py::arg("antialiasing") = false)
+        .def_readonly("antialiasing", &gsr::RasterSettings::antialiasing);
     m.def(
         "rasterize_gaussians",
         [](const gsr::RasterCamera& cam, const gsr::RasterSettings& rs, torch::Tensor means3D, torch::Tensor means2D,

@@ -15,7 +15,8 @@
 // (features_dc_ / features_rest_, gaussian_model.h:12-14 -- passed separately so the
 // get_features() cat copy, gaussian_model.cpp:289-292, is never made) and get_max_sh_degree().
 // `Pipe` is PipelineParams (src/arguments/params.h:93-106): convert_SHs_python_,
-// compute_cov3D_python_, debug_.
+// compute_cov3D_python_, debug_.  The reference's PipelineParams has no anti-aliasing member, so
+// that switch (upstream's `antialiasing`, gsr.h GSR_FLAG_ANTIALIAS) is render()'s last argument.
 #pragma once
 #include <torch/torch.h>
 
@@ -55,6 +56,7 @@ struct RasterSettings {
     int tile_y0 = 0, tile_y1 = INT32_MAX;  // tile-row band
     bool debug = false;
     int max_rendered = 0;  // > 0: binning sized for this many instances, no host read (gsr.h)
+    bool antialiasing = false;  // GSR_FLAG_ANTIALIAS: blend o' = o sqrt(det(cov2D) / det(cov2D + 0.3 I)) (gsr.h)
 };
 
 struct RenderOutput {
@@ -145,7 +147,8 @@ torch::Tensor eval_sh_colors(int D, const torch::Tensor& sh, const torch::Tensor
 template <class Model, class Pipe>
 RenderOutput render(const RasterCamera& cam, Model& pc, const Pipe& pipe, const std::array<float, 3>& bg,
                     float scaling_modifier = 1.f, std::optional<torch::Tensor> override_color = std::nullopt,
-                    BinningCapacity* binning = nullptr, bool return_depth = false, bool inverse_depth = false) {
+                    BinningCapacity* binning = nullptr, bool return_depth = false, bool inverse_depth = false,
+                    bool antialiasing = false) {
     const auto& xyz = pc.get_xyz();
     auto screenspace = torch::zeros_like(xyz).requires_grad_(true);
     RasterSettings rs;
@@ -155,6 +158,7 @@ RenderOutput render(const RasterCamera& cam, Model& pc, const Pipe& pipe, const 
     rs.sh_degree = core.active_sh_degree_;
     rs.debug = pipe.debug_;
     rs.max_rendered = binning ? binning->bound() : 0;
+    rs.antialiasing = antialiasing;
     torch::Tensor scales, rotations, cov3D, sh_dc, sh_rest, colors;
     // The reference's GaussianModel::get_covariance takes an int modifier
     // (gaussian_model.h:89), so it is called only with an integral one; any other modifier is
@@ -208,9 +212,10 @@ RenderOutput render(const RasterCamera& cam, Model& pc, const Pipe& pipe, const 
 template <class Model, class Pipe>
 RenderOutput render(const RasterCamera& cam, Model& pc, const Pipe& pipe, const torch::Tensor& bg,
                     float scaling_modifier = 1.f, std::optional<torch::Tensor> override_color = std::nullopt,
-                    BinningCapacity* binning = nullptr, bool return_depth = false, bool inverse_depth = false) {
+                    BinningCapacity* binning = nullptr, bool return_depth = false, bool inverse_depth = false,
+                    bool antialiasing = false) {
     return render(cam, pc, pipe, background(bg), scaling_modifier, std::move(override_color), binning, return_depth,
-                  inverse_depth);
+                  inverse_depth, antialiasing);
 }
 
 namespace detail {

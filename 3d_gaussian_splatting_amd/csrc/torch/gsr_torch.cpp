@@ -72,7 +72,7 @@ gsr_raster_settings make_settings(const RasterSettings& rs) {
     for (int c = 0; c < 3; ++c) s.bg[c] = rs.bg[c];
     s.tile_y0 = rs.tile_y0;
     s.tile_y1 = rs.tile_y1;
-    s.flags = rs.debug ? GSR_FLAG_DEBUG : 0u;
+    s.flags = (rs.debug ? GSR_FLAG_DEBUG : 0u) | (rs.antialiasing ? GSR_FLAG_ANTIALIAS : 0u);
     s.max_rendered = rs.max_rendered;
     return s;
 }
@@ -192,7 +192,7 @@ void save_frame(AutogradContext* ctx, const RasterCamera& cam, const RasterSetti
     // restore_frame reads the integers and the scalars back by position
     ctx->saved_data["ints"] = std::vector<int64_t>{r.bufs.num_rendered, r.bufs.capacity, r.bufs.n_local, r.bufs.layout,
                                                    present(means2D), cam.width, cam.height, rs.sh_degree, rs.tile_y0,
-                                                   rs.tile_y1, rs.debug, rs.max_rendered};
+                                                   rs.tile_y1, rs.debug, rs.max_rendered, rs.antialiasing};
     ctx->saved_data["scalars"] = std::vector<double>{cam.tanfovx, cam.tanfovy, rs.scale_modifier};
     ctx->saved_data["cam_v"] = doubles(cam.viewmatrix);
     ctx->saved_data["cam_p"] = doubles(cam.projmatrix);
@@ -212,7 +212,7 @@ SavedFrame restore_frame(AutogradContext* ctx) {
     f.has_m2d = n[4] != 0;
     f.cam.width = (int)n[5], f.cam.height = (int)n[6];
     f.rs.sh_degree = (int)n[7], f.rs.tile_y0 = (int)n[8], f.rs.tile_y1 = (int)n[9];
-    f.rs.debug = n[10] != 0, f.rs.max_rendered = (int)n[11];
+    f.rs.debug = n[10] != 0, f.rs.max_rendered = (int)n[11], f.rs.antialiasing = n[12] != 0;
     f.cam.tanfovx = (float)x[0], f.cam.tanfovy = (float)x[1], f.rs.scale_modifier = (float)x[2];
     floats("cam_v", f.cam.viewmatrix);
     floats("cam_p", f.cam.projmatrix);

@@ -27,6 +27,8 @@ GSR_FLAG_AUX = 4        # gsr.h: implied by gsr_forward_aux / gsr_backward_aux
 GSR_FLAG_INVDEPTH = 8   # gsr.h: the aux depth channel blends 1 / z
 GSR_LAYOUT_AUX = 4      # gsr_buffers.layout bits written by gsr_forward_aux
 GSR_LAYOUT_INVDEPTH = 8
+GSR_FLAG_ANTIALIAS = 16    # gsr.h: blend o' = o sqrt(max(0.000025, det(cov2D) / det(cov2D + 0.3 I)))
+GSR_LAYOUT_ANTIALIAS = 16  # gsr_buffers.layout bit of a forward that ran with GSR_FLAG_ANTIALIAS
 GSR_ERR_LAYOUT = -13
 GSR_ERR_OVERFLOW = -4
 GSR_GRAD2D_STRIDE = 12

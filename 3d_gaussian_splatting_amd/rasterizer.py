@@ -198,7 +198,7 @@ class CAbiRasterizer:
             raise RuntimeError(f"{what} failed ({rc}): {native.last_error()}")
 
     def _prepare(self, means3D, opacities, scales, rotations, sh_dc, sh_rest, sh_degree, colors_precomp,
-                 cov3D_precomp, scale_modifier, bg, tile_rows, max_rendered, debug):
+                 cov3D_precomp, scale_modifier, bg, tile_rows, max_rendered, debug, antialiasing=False):
         dev = self.device
         means3D = _f32(means3D, device=dev)
         P = int(means3D.shape[0])
@@ -222,7 +222,8 @@ class CAbiRasterizer:
         s = native.Settings()
         s.bg[:] = [float(v) for v in bg]
         s.tile_y0, s.tile_y1 = (0, INT32_MAX) if tile_rows is None else (int(tile_rows[0]), int(tile_rows[1]))
-        s.flags = native.GSR_FLAG_DEBUG if debug else 0
+        # the state keeps these settings, so every backward passes the forward's flags
+        s.flags = (native.GSR_FLAG_DEBUG if debug else 0) | (native.GSR_FLAG_ANTIALIAS if antialiasing else 0)
         s.max_rendered = int(max_rendered)
         return inputs, g, s
 
@@ -251,21 +252,24 @@ class CAbiRasterizer:
 
     def forward(self, cam: RasterCamera, means3D, opacities, scales=None, rotations=None, sh_dc=None,
                 sh_rest=None, sh_degree=0, colors_precomp=None, cov3D_precomp=None, scale_modifier=1.0,
-                bg=(0.0, 0.0, 0.0), tile_rows=None, max_rendered=0, debug=False) -> ForwardState:
+                bg=(0.0, 0.0, 0.0), tile_rows=None, max_rendered=0, debug=False,
+                antialiasing=False) -> ForwardState:
         """gsr_forward.  max_rendered > 0 sizes the binning for that many instances and skips the
-        host read of K (see ForwardState.num_rendered)."""
+        host read of K (see ForwardState.num_rendered).  antialiasing: GSR_FLAG_ANTIALIAS, the
+        opacity compensation for the 0.3 px^2 dilation; the returned state carries it to backward()."""
         return self._forward(cam, None, means3D, opacities, scales, rotations, sh_dc, sh_rest, sh_degree,
-                             colors_precomp, cov3D_precomp, scale_modifier, bg, tile_rows, max_rendered, debug)
+                             colors_precomp, cov3D_precomp, scale_modifier, bg, tile_rows, max_rendered, debug,
+                             antialiasing)
 
     def forward_aux(self, cam: RasterCamera, means3D, opacities, scales=None, rotations=None, sh_dc=None,
                     sh_rest=None, sh_degree=0, colors_precomp=None, cov3D_precomp=None, scale_modifier=1.0,
                     bg=(0.0, 0.0, 0.0), tile_rows=None, max_rendered=0, debug=False,
-                    inverse_depth=False) -> ForwardState:
+                    inverse_depth=False, antialiasing=False) -> ForwardState:
         """gsr_forward_aux: forward() plus .depth = sum w z (sum w / z with inverse_depth) and
         .alpha = sum w per pixel, over the pairs the colour pass blends.  Full images only."""
         return self._forward(cam, bool(inverse_depth), means3D, opacities, scales, rotations, sh_dc, sh_rest,
                              sh_degree, colors_precomp, cov3D_precomp, scale_modifier, bg, tile_rows, max_rendered,
-                             debug)
+                             debug, antialiasing)
 
     def _backward(self, st: ForwardState, dL_dpix, aux_grads=None) -> dict:
         """gsr_backward, or gsr_backward_aux with aux_grads = (dL_ddepth, dL_dalpha), each None = zero."""
@@ -292,12 +296,13 @@ class CAbiRasterizer:
 
     def forward_batch(self, cams, means3D, opacities, scales=None, rotations=None, sh_dc=None, sh_rest=None,
                       sh_degree=0, colors_precomp=None, cov3D_precomp=None, scale_modifier=1.0,
-                      bg=(0.0, 0.0, 0.0), max_rendered=0, debug=False) -> list:
+                      bg=(0.0, 0.0, 0.0), max_rendered=0, debug=False, antialiasing=False) -> list:
         """gsr_forward_batch: one ForwardState per camera (full images), one host wait in total
         (none with max_rendered > 0)."""
         dev = self.device
         inputs, g, s = self._prepare(means3D, opacities, scales, rotations, sh_dc, sh_rest, sh_degree,
-                                     colors_precomp, cov3D_precomp, scale_modifier, bg, None, max_rendered, debug)
+                                     colors_precomp, cov3D_precomp, scale_modifier, bg, None, max_rendered, debug,
+                                     antialiasing)
         V, P = len(cams), g.P
         colors = [torch.empty((3, c.height, c.width), dtype=torch.float32, device=dev) for c in cams]
         radii = [torch.empty((P,), dtype=torch.int32, device=dev) for _ in cams]
@@ -319,12 +324,13 @@ class CAbiRasterizer:
 
     def forward_views(self, cams, means3D, opacities, scales=None, rotations=None, sh_dc=None, sh_rest=None,
                       sh_degree=0, colors_precomp=None, cov3D_precomp=None, scale_modifier=1.0,
-                      bg=(0.0, 0.0, 0.0), max_rendered=0, debug=False) -> "ViewsState":
+                      bg=(0.0, 0.0, 0.0), max_rendered=0, debug=False, antialiasing=False) -> "ViewsState":
         """gsr_forward_views: V same-size cameras in one pass (one launch per stage).  color is
         V x 3 x H x W, radii V x P; bit-identical to V forward() calls."""
         dev = self.device
         inputs, g, s = self._prepare(means3D, opacities, scales, rotations, sh_dc, sh_rest, sh_degree,
-                                     colors_precomp, cov3D_precomp, scale_modifier, bg, None, max_rendered, debug)
+                                     colors_precomp, cov3D_precomp, scale_modifier, bg, None, max_rendered, debug,
+                                     antialiasing)
         V, P = len(cams), g.P
         H, W = cams[0].height, cams[0].width
         color = torch.empty((V, 3, H, W), dtype=torch.float32, device=dev)
@@ -565,21 +571,21 @@ def ext_camera(cam: RasterCamera):
                             [float(v) for v in cam.campos])
 
 
-def _ext_settings(ext, bg, scale_modifier, sh_degree, tile_rows, debug, max_rendered):
+def _ext_settings(ext, bg, scale_modifier, sh_degree, tile_rows, debug, max_rendered, antialiasing=False):
     y0, y1 = (0, INT32_MAX) if tile_rows is None else tile_rows
     return ext.RasterSettings([float(v) for v in bg], float(scale_modifier), int(sh_degree), int(y0), int(y1),
-                              bool(debug), int(max_rendered))
+                              bool(debug), int(max_rendered), bool(antialiasing))
 
 
 def rasterize_gaussians_aux(cam: RasterCamera, means3D, means2D, opacities, sh_dc=None, sh_rest=None,
                             colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None,
                             sh_degree=0, scale_modifier=1.0, bg=(0.0, 0.0, 0.0), tile_rows=None, debug=False,
-                            max_rendered=0, inverse_depth=False):
+                            max_rendered=0, inverse_depth=False, antialiasing=False):
     """RasterizeGaussiansAux.apply: returns (color (3,H,W), depth (H,W), alpha (H,W), radii (P,)
     int32).  color, depth and alpha are differentiable in every tensor input; depth = sum w z
     (sum w / z with inverse_depth), alpha = sum w, un-normalised (expected depth = depth / alpha)."""
     ext = native.load_torch_ext()
-    rs = _ext_settings(ext, bg, scale_modifier, sh_degree, tile_rows, debug, max_rendered)
+    rs = _ext_settings(ext, bg, scale_modifier, sh_degree, tile_rows, debug, max_rendered, antialiasing)
     return ext.rasterize_gaussians_aux(ext_camera(cam), rs, bool(inverse_depth), means3D, means2D, sh_dc, sh_rest,
                                        colors_precomp, opacities, scales, rotations, cov3D_precomp)
 
@@ -587,11 +593,12 @@ def rasterize_gaussians_aux(cam: RasterCamera, means3D, means2D, opacities, sh_d
 def rasterize_gaussians(cam: RasterCamera, means3D, means2D, opacities, sh_dc=None, sh_rest=None,
                         colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None,
                         sh_degree=0, scale_modifier=1.0, bg=(0.0, 0.0, 0.0), tile_rows=None, debug=False,
-                        max_rendered=0):
+                        max_rendered=0, antialiasing=False):
     """RasterizeGaussians.apply: returns (color (3,H,W), radii (P,) int32); differentiable in
-    every tensor input (means2D receives the screen-space gradient)."""
+    every tensor input (means2D receives the screen-space gradient).  antialiasing: upstream's
+    rasterization setting of that name (gsr.h GSR_FLAG_ANTIALIAS), carried to the backward."""
     ext = native.load_torch_ext()
-    rs = _ext_settings(ext, bg, scale_modifier, sh_degree, tile_rows, debug, max_rendered)
+    rs = _ext_settings(ext, bg, scale_modifier, sh_degree, tile_rows, debug, max_rendered, antialiasing)
     return ext.rasterize_gaussians(ext_camera(cam), rs, means3D, means2D, sh_dc, sh_rest, colors_precomp,
                                    opacities, scales, rotations, cov3D_precomp)
 
@@ -615,6 +622,7 @@ class PipelineParams:
     convert_SHs_python: bool = False
     compute_cov3D_python: bool = False
     debug: bool = False
+    antialiasing: bool = False  # upstream 3DGS's PipelineParams.antialiasing (the reference's struct has none)
 
 
 def render(viewpoint_camera: RasterCamera, pc, pipe: PipelineParams, bg_color, scaling_modifier=1.0,
@@ -622,7 +630,8 @@ def render(viewpoint_camera: RasterCamera, pc, pipe: PipelineParams, bg_color, s
     """render(): same contract as the C++ gsr::render template (csrc/torch/gsr_render.h) for a
     model exposing the reference GaussianModel getters (see model.GaussianModel).  return_depth
     adds the differentiable keys "depth" (sum w z, or sum w / z with inverse_depth) and "alpha"
-    (sum w); without it the dict and the kernels launched are the colour-only ones."""
+    (sum w); without it the dict and the kernels launched are the colour-only ones.
+    pipe.antialiasing renders with the opacity compensation (gsr.h GSR_FLAG_ANTIALIAS)."""
     from .general import eval_sh
     xyz = pc.get_xyz
     screenspace = torch.zeros_like(xyz, requires_grad=True)
@@ -643,7 +652,7 @@ def render(viewpoint_camera: RasterCamera, pc, pipe: PipelineParams, bg_color, s
         sh_dc, sh_rest = pc.features_dc, pc.features_rest
     kw = dict(sh_dc=sh_dc, sh_rest=sh_rest, colors_precomp=colors, scales=scales, rotations=rotations,
               cov3D_precomp=cov3D, sh_degree=0 if colors is not None else pc.active_sh_degree,
-              scale_modifier=scaling_modifier, bg=bg, debug=pipe.debug)
+              scale_modifier=scaling_modifier, bg=bg, debug=pipe.debug, antialiasing=getattr(pipe, "antialiasing", False))
     if return_depth:
         color, depth, alpha, radii = rasterize_gaussians_aux(viewpoint_camera, xyz, screenspace, pc.get_opacity,
                                                              inverse_depth=inverse_depth, **kw)

@@ -86,6 +86,9 @@ class OptimizationParams:
     depth_inverse: bool = True        # supervise sum w / z (upstream's invDepth)
     depth_normalized: bool = False    # pred = depth / alpha where alpha >= depth_alpha_min
     depth_alpha_min: float = 0.5      # a design default, not a tuned value
+    # anti-aliased rendering (upstream's `antialiasing`; the reference's struct has none): every
+    # render of step() blends the compensated opacity (gsr.h GSR_FLAG_ANTIALIAS)
+    antialiasing: bool = False
 
 
 def _device(device) -> torch.device:
@@ -471,7 +474,7 @@ class GaussianTrainer:
         p = self.params
         bound = self.binning.bound()
         kw = dict(scales=s, rotations=q, sh_dc=p["f_dc"], sh_rest=p["f_rest"] if p["f_rest"].shape[1] else None,
-                  sh_degree=self.active_sh_degree, bg=bg, max_rendered=bound)
+                  sh_degree=self.active_sh_degree, bg=bg, max_rendered=bound, antialiasing=self.opt.antialiasing)
         if aux:
             st = self.rast.forward_aux(cam, p["xyz"], o.reshape(-1), inverse_depth=self.opt.depth_inverse, **kw)
         else:

@@ -65,6 +65,21 @@ extern "C" {
  * instead of z. */
 #define GSR_FLAG_AUX 4u
 #define GSR_FLAG_INVDEPTH 8u
+/* Anti-aliased rendering (the Mip-Splatting opacity compensation; upstream's `antialiasing`
+ * rasterization setting).  With (a0, b, c0) the EWA 2D covariance before the 0.3 px^2 dilation,
+ *   coef = sqrtf(max(0.000025f, (a0 c0 - b^2) / ((a0 + 0.3)(c0 + 0.3) - b^2))),   o' = o * coef
+ * and everything after F1 that uses the opacity uses o' (the record's o and log2 o, its footprint
+ * extents).  The conic, radii, rect, tiles and depth keys, hence K, the sorted list and the ranges,
+ * are bit-identical to the unflagged call's.  Honoured by gsr_forward, gsr_forward_aux,
+ * gsr_forward_views and gsr_forward_batch, which record GSR_LAYOUT_ANTIALIAS in bufs->layout; every
+ * backward that takes those buffers must be given the same flag (gsr_backward, gsr_backward_blend,
+ * gsr_backward_preprocess, gsr_backward_aux, gsr_backward_views: a disagreement between rs->flags and
+ * the layout bit is GSR_ERR_LAYOUT, before any allocation or launch).  The backward then chains
+ * dL/do' to dL/do = coef dL/do' and, through coef, to the covariance (scales, rotations or cov3D) and
+ * the mean; the gradient through coef is zero where the 0.000025 clamp holds.  dL_dconic keeps its
+ * meaning.  The multi-GPU calls (gsr_shard_*, gsr_band_*) render without compensation only: they
+ * refuse the flag (< 0) before any device work. */
+#define GSR_FLAG_ANTIALIAS 16u
 #define GSR_ERR_OVERFLOW (-4) /* gsr_read_num_rendered: K exceeded the binning's capacity */
 
 typedef struct gsr_camera {
@@ -138,7 +153,8 @@ typedef struct gsr_buffers {
 #define GSR_LAYOUT_AUX 4u                /* written by gsr_forward_aux: the image / binning buffers are the
                                            larger aux ones (depth sum plane, depth checkpoints) */
 #define GSR_LAYOUT_INVDEPTH 8u          /* with GSR_LAYOUT_AUX: that forward ran with GSR_FLAG_INVDEPTH */
-#define GSR_ERR_LAYOUT (-13)            /* gsr_buffers.layout missing or inconsistent */
+#define GSR_LAYOUT_ANTIALIAS 16u        /* that forward ran with GSR_FLAG_ANTIALIAS: its records carry o' */
+#define GSR_ERR_LAYOUT (-13)           /* gsr_buffers.layout missing or inconsistent */
 
 int gsr_abi_version(void);
 const char* gsr_last_error(void);
