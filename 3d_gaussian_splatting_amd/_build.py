@@ -2,7 +2,7 @@
 
   lib/libgsr_hip.so      hipcc --offload-arch=gfx950: the CDNA4 kernels + the C ABI
   lib/_gsr_torch*.so     libtorch render() + autograd Function (C++), links libgsr_hip.so
-  lib/gsr_dropin, gsr_train_loop, gsr_shard_step   C++ executables over the same libtorch layer
+  lib/gsr_dropin, gsr_sparse_adam, gsr_train_loop, gsr_shard_step   C++ executables over the same libtorch layer
 
 The libtorch layer (csrc/torch/) is compiled once, position-independent, into lib/obj/*.o; the
 extension links those objects plus gsr_bind.cpp (the only pybind11 file), the executables link
@@ -267,6 +267,13 @@ def build_dropin(verbose: bool = False, force: bool = False) -> str:
     return _build_exe("gsr_dropin", os.path.join(ROOT, "tests", "cpp", "dropin_main.cpp"), force)
 
 
+def build_sparse_adam(verbose: bool = False, force: bool = False) -> str:
+    """tests/cpp/sparse_adam_main.cpp + the libtorch layer into lib/gsr_sparse_adam: the
+    visibility-masked gsr::fused_adam_step on torch::optim::Adam state, checked against the dense
+    one (tests/test_gpu_sparse_adam.py)."""
+    return _build_exe("gsr_sparse_adam", os.path.join(ROOT, "tests", "cpp", "sparse_adam_main.cpp"), force)
+
+
 def build_train_loop(verbose: bool = False, force: bool = False) -> str:
     """tests/cpp/train_main.cpp + the libtorch layer into lib/gsr_train_loop: the reference's
     train() loop (train_utils.cpp:128-145) over gsr::Trainer (tests/test_gpu_train_loop.py,
@@ -284,6 +291,7 @@ def build_all(verbose: bool = False, force: bool = False):
     so = build_hip(verbose, force)
     ext = build_torch_ext(verbose, force)
     build_dropin(verbose, force)
+    build_sparse_adam(verbose, force)
     build_train_loop(verbose, force)
     build_shard_step(verbose, force)
     return so, ext

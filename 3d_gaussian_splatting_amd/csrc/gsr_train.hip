@@ -17,6 +17,9 @@
 //                         double by depth_loss_finalize_kernel (fixed order, no atomics).
 //  * adam_kernel          one launch for all six parameter groups (multi-tensor): activation
 //                         backward, moments, bias-corrected update; float4 per thread.
+//  * adam_sparse_kernel   the same step for the rows of Gaussians with radii > 0 only: a block reads
+//                         its span's radii into an LDS bitmap and fetches only the float4 pieces
+//                         that overlap a visible row.
 //  * densify_stats_kernel max_radii2D / grad accumulation / denom for radii > 0.
 //  * compact_* + gather_rows_kernel  mask -> ascending index list (wave64 ballot counts,
 //                         block-local scan) and a multi-tensor row gather (prune / clone).
@@ -551,6 +554,106 @@ __global__ __launch_bounds__(kAdamBlock) void adam_kernel(const AdamArgs a) {
     }
 }
 
+// The visibility-masked step (gsr_adam_step_sparse): rows of Gaussians with radii <= 0 keep their
+// bytes and are not fetched.  A block owns one group and a span of Gaussians that starts on a
+// multiple of 4 (so the span's first float is float4-aligned for every row width); the host
+// sizes the span so that the block walks about kSparseIters float4 pieces per thread.
+constexpr int kSparseIters = 3, kSparseSpanMax = 1024;
+struct AdamSparseArgs {
+    AdamArgs a;
+    const int* radii;
+    int P;
+    int width[GSR_ADAM_MAX_GROUPS];  // floats per Gaussian (n / P)
+    int span[GSR_ADAM_MAX_GROUPS];   // Gaussians per block: a multiple of 4, <= kSparseSpanMax
+};
+
+// The span's radii first (coalesced, one ballot per wave into an LDS bitmap); a span without a
+// visible row ends there.  Otherwise the span's flat float4 pieces as adam_kernel walks them, a
+// piece's four arrays loaded only when it overlaps a visible row.  A piece that straddles a
+// visible and an invisible row (widths that are no multiple of 4) stores the loaded bits back
+// for the invisible elements: a select, so that a NaN computed from an invisible row's gradient
+// never reaches memory.
+__global__ __launch_bounds__(kAdamBlock) void adam_sparse_kernel(const AdamSparseArgs s) {
+    const AdamArgs& a = s.a;
+    if (guard_tripped(a.guard_k, a.guard_cap)) return;
+    int gi = 0;
+    while (gi + 1 < a.ngroups && (int)blockIdx.x >= a.blk_start[gi + 1]) ++gi;  // wave-uniform
+    const gsr_adam_group& G = a.g[gi];
+    const float ss = a.step_size[gi], b2s = a.bc2_sqrt[gi];
+    const int width = s.width[gi], span = s.span[gi];
+    const int g0 = (int)(blockIdx.x - a.blk_start[gi]) * span;
+    const int len = min(span, s.P - g0);
+    __shared__ unsigned long long vis[kSparseSpanMax / 64 + 1];  // + 1: the row after a full span's last
+    bool mine = false;
+    for (int j0 = 0; j0 < len; j0 += kAdamBlock) {  // block-uniform trip count
+        const int j = j0 + (int)threadIdx.x;
+        const bool on = j < len && s.radii[g0 + j] > 0;
+        const unsigned long long bits = __ballot(on);
+        if ((threadIdx.x & 63) == 0) vis[j >> 6] = bits;
+        mine |= on;
+    }
+    if (!__syncthreads_or(mine)) return;
+    float* const P_ = G.param + (long long)g0 * width;
+    const float* const G_ = G.grad + (long long)g0 * width;
+    float* const M_ = G.exp_avg + (long long)g0 * width;
+    float* const V_ = G.exp_avg_sq + (long long)g0 * width;
+    const int nel = len * width;  // < 2^31 (host check)
+    for (int e0 = (int)threadIdx.x * 4; e0 < nel; e0 += 4 * kAdamBlock) {
+        const int cnt = min(4, nel - e0);
+        int row = (int)((unsigned)e0 / (unsigned)width), col = e0 - row * width;
+        bool on[4], any = false;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            on[k] = k < cnt && ((vis[row >> 6] >> (row & 63)) & 1ull);
+            any |= on[k];
+            if (++col == width) col = 0, ++row;
+        }
+        if (!any) continue;
+        float p[4], g[4], m[4], v[4];
+        if (cnt == 4) {
+            const float4 P4 = ld4(P_ + e0);
+            const float4 G4 = ld4(G_ + e0);
+            const float4 M4 = ld4(M_ + e0);
+            const float4 V4 = ld4(V_ + e0);
+            p[0] = P4.x, p[1] = P4.y, p[2] = P4.z, p[3] = P4.w;
+            g[0] = G4.x, g[1] = G4.y, g[2] = G4.z, g[3] = G4.w;
+            m[0] = M4.x, m[1] = M4.y, m[2] = M4.z, m[3] = M4.w;
+            v[0] = V4.x, v[1] = V4.y, v[2] = V4.z, v[3] = V4.w;
+        } else {
+            for (int k = 0; k < 4; ++k) {
+                const bool in = k < cnt;
+                p[k] = in ? P_[e0 + k] : 0.f;
+                g[k] = in ? G_[e0 + k] : 0.f;
+                m[k] = in ? M_[e0 + k] : 0.f;
+                v[k] = in ? V_[e0 + k] : 0.f;
+            }
+        }
+        const float p0[4] = {p[0], p[1], p[2], p[3]}, m0[4] = {m[0], m[1], m[2], m[3]},
+                    v0[4] = {v[0], v[1], v[2], v[3]};
+        adam_act_grad(G.act, p, g);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) adam_one(p[k], g[k], m[k], v[k], ss, b2s, a);
+        if (cnt == 4) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                p[k] = on[k] ? p[k] : p0[k];
+                m[k] = on[k] ? m[k] : m0[k];
+                v[k] = on[k] ? v[k] : v0[k];
+            }
+            st4(P_ + e0, make_float4(p[0], p[1], p[2], p[3]));
+            st4(M_ + e0, make_float4(m[0], m[1], m[2], m[3]));
+            st4(V_ + e0, make_float4(v[0], v[1], v[2], v[3]));
+        } else {
+            for (int k = 0; k < cnt; ++k) {
+                if (!on[k]) continue;
+                P_[e0 + k] = p[k];
+                M_[e0 + k] = m[k];
+                V_[e0 + k] = v[k];
+            }
+        }
+    }
+}
+
 // ---------------------------------------------------------------- densification statistics
 __global__ __launch_bounds__(256) void densify_stats_kernel(const int* __restrict__ radii, const float* __restrict__ dm2,
                                                             int P, float* __restrict__ maxr, float* __restrict__ acc,
@@ -771,12 +874,11 @@ int gsr_adam_step(const gsr_adam_group* groups, int32_t ngroups, float beta1, fl
     return gsr_adam_step_guarded(groups, ngroups, beta1, beta2, eps, nullptr, 0, stream);
 }
 
-int gsr_adam_step_guarded(const gsr_adam_group* groups, int32_t ngroups, float beta1, float beta2, float eps,
-                          const uint32_t* guard_k, uint32_t guard_cap, void* stream) {
-    if (ngroups < 0 || ngroups > GSR_ADAM_MAX_GROUPS) return set_error(-1, "adam: 0..8 groups");
-    if (ngroups == 0) return 0;
+// The checks and the per-group scalars the dense and the sparse step share: everything of AdamArgs
+// but blk_start (1 <= ngroups <= GSR_ADAM_MAX_GROUPS).  0, or < 0 with the error text set.
+static int adam_fill_args(AdamArgs& a, const gsr_adam_group* groups, int32_t ngroups, float beta1, float beta2, float eps,
+                          const uint32_t* guard_k, uint32_t guard_cap) {
     if (!groups) return set_error(-1, "adam: null groups");
-    AdamArgs a;
     std::memset(&a, 0, sizeof a);
     a.ngroups = ngroups;
     a.b1 = beta1;
@@ -786,7 +888,6 @@ int gsr_adam_step_guarded(const gsr_adam_group* groups, int32_t ngroups, float b
     a.omb2 = (float)(1.0 - (double)beta2);
     a.guard_k = guard_k;
     a.guard_cap = guard_cap;
-    long long blocks = 0;
     for (int i = 0; i < ngroups; ++i) {
         const gsr_adam_group& g = groups[i];
         if (g.n < 0) return set_error(-1, "adam: negative group size");
@@ -797,18 +898,65 @@ int gsr_adam_step_guarded(const gsr_adam_group* groups, int32_t ngroups, float b
         for (const void* p : {(const void*)g.param, (const void*)g.grad, (const void*)g.exp_avg, (const void*)g.exp_avg_sq})
             if (reinterpret_cast<uintptr_t>(p) & 15) return set_error(-1, "adam: tensors must be 16-byte aligned");
         a.g[i] = g;
-        a.blk_start[i] = (int)blocks;
-        blocks += (g.n + kAdamPerBlock - 1) / kAdamPerBlock;
         // libtorch adam.cpp: bias corrections in double, scalars cast to the tensor type
         const double bc1 = 1.0 - std::pow((double)beta1, (double)g.step);
         const double bc2 = 1.0 - std::pow((double)beta2, (double)g.step);
         a.step_size[i] = (float)((double)g.lr / bc1);
         a.bc2_sqrt[i] = (float)std::sqrt(bc2);
     }
-    if (blocks > INT32_MAX / 2) return set_error(-1, "adam: too many elements");
+    return 0;
+}
+
+int gsr_adam_step_guarded(const gsr_adam_group* groups, int32_t ngroups, float beta1, float beta2, float eps,
+                          const uint32_t* guard_k, uint32_t guard_cap, void* stream) {
+    if (ngroups < 0 || ngroups > GSR_ADAM_MAX_GROUPS) return set_error(-1, "adam: 0..8 groups");
+    if (ngroups == 0) return 0;
+    AdamArgs a;
+    if (const int rc = adam_fill_args(a, groups, ngroups, beta1, beta2, eps, guard_k, guard_cap)) return rc;
+    long long blocks = 0;
+    for (int i = 0; i < ngroups; ++i) {
+        a.blk_start[i] = (int)blocks;
+        blocks += (a.g[i].n + kAdamPerBlock - 1) / kAdamPerBlock;
+        if (blocks > INT32_MAX / 2) return set_error(-1, "adam: too many elements");
+    }
     a.blk_start[ngroups] = (int)blocks;
     if (blocks == 0) return 0;
     hipLaunchKernelGGL(adam_kernel, dim3((unsigned)blocks), dim3(kAdamBlock), 0, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+}
+
+int gsr_adam_step_sparse(const gsr_adam_group* groups, int32_t ngroups, const int32_t* radii, int32_t P, float beta1,
+                         float beta2, float eps, const uint32_t* guard_k, uint32_t guard_cap, void* stream) {
+    if (ngroups < 0 || ngroups > GSR_ADAM_MAX_GROUPS) return set_error(-1, "adam: 0..8 groups");
+    if (P < 0) return set_error(-1, "adam: negative P");
+    if (ngroups == 0 || P == 0) return 0;
+    if (!radii) return set_error(-1, "adam: null radii");
+    AdamSparseArgs s;
+    std::memset(&s, 0, sizeof s);
+    if (const int rc = adam_fill_args(s.a, groups, ngroups, beta1, beta2, eps, guard_k, guard_cap)) return rc;
+    s.radii = radii;
+    s.P = P;
+    long long blocks = 0;
+    for (int i = 0; i < ngroups; ++i) {
+        const gsr_adam_group& g = s.a.g[i];
+        s.a.blk_start[i] = (int)blocks;
+        if (g.n == 0) continue;  // e.g. f_rest at SH degree 0
+        if (g.n % P) return set_error(-1, "adam: group size is no multiple of P");
+        const long long width = g.n / P;
+        if (g.act == GSR_ACT_NORMALIZE4 && width % 4) return set_error(-1, "adam: normalize group needs rows of 4");
+        if (width >= (1ll << 28)) return set_error(-1, "adam: row too wide");  // 4 rows' floats stay in int32
+        // about kSparseIters float4 pieces per thread; 4 | span keeps every span float4-aligned
+        long long span = (long long)kSparseIters * kAdamPerBlock / width;
+        span = (span < kSparseSpanMax ? span : kSparseSpanMax) & ~3ll;
+        if (span < 4) span = 4;
+        s.width[i] = (int)width;
+        s.span[i] = (int)span;
+        blocks += (P + span - 1) / span;
+    }
+    if (blocks > INT32_MAX / 2) return set_error(-1, "adam: too many elements");
+    s.a.blk_start[ngroups] = (int)blocks;
+    if (blocks == 0) return 0;
+    hipLaunchKernelGGL(adam_sparse_kernel, dim3((unsigned)blocks), dim3(kAdamBlock), 0, (hipStream_t)stream, s);
     return (int)hipGetLastError();
 }
 

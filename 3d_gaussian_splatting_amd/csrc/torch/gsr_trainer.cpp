@@ -144,18 +144,25 @@ std::pair<const uint32_t*, uint32_t> guard_of(const RenderOutput* r) {
     if (!r || r->num_rendered >= 0 || !r->num_rendered_device.defined()) return {nullptr, 0u};
     return {reinterpret_cast<const uint32_t*>(r->num_rendered_device.data_ptr<int32_t>()), (uint32_t)r->capacity};
 }
-}  // namespace
 
-void fused_adam_step(const std::vector<torch::optim::Adam*>& optimizers, const RenderOutput* guard) {
+// The libtorch state handling of both fused steps; radii == nullptr: the dense step, otherwise
+// the visibility-masked one over P Gaussians.
+void fused_adam_step_impl(const std::vector<torch::optim::Adam*>& optimizers, const int32_t* radii, int64_t P,
+                          const RenderOutput* guard) {
     std::vector<gsr_adam_group> groups;
     std::vector<torch::Tensor> keep;
     double beta1 = -1, beta2 = -1, eps = -1;
     const auto gk = guard_of(guard);
     auto launch = [&]() {
         if (groups.empty()) return;
-        check(gsr_adam_step_guarded(groups.data(), (int32_t)groups.size(), (float)beta1, (float)beta2, (float)eps,
-                                    gk.first, gk.second, stream()),
-              "gsr_adam_step");
+        if (radii)
+            check(gsr_adam_step_sparse(groups.data(), (int32_t)groups.size(), radii, (int32_t)P, (float)beta1,
+                                       (float)beta2, (float)eps, gk.first, gk.second, stream()),
+                  "gsr_adam_step_sparse");
+        else
+            check(gsr_adam_step_guarded(groups.data(), (int32_t)groups.size(), (float)beta1, (float)beta2, (float)eps,
+                                        gk.first, gk.second, stream()),
+                  "gsr_adam_step");
         groups.clear();
         keep.clear();
     };
@@ -199,6 +206,25 @@ void fused_adam_step(const std::vector<torch::optim::Adam*>& optimizers, const R
         }
     }
     launch();
+}
+}  // namespace
+
+void fused_adam_step(const std::vector<torch::optim::Adam*>& optimizers, const RenderOutput* guard) {
+    fused_adam_step_impl(optimizers, nullptr, 0, guard);
+}
+
+void fused_adam_step(const std::vector<torch::optim::Adam*>& optimizers, const torch::Tensor& radii,
+                     const RenderOutput* guard) {
+    TORCH_CHECK(radii.defined() && radii.is_cuda() && radii.scalar_type() == torch::kInt32 && radii.is_contiguous(),
+                "fused_adam_step: radii must be a contiguous int32 CUDA tensor");
+    const int64_t P = radii.numel();
+    TORCH_CHECK(P > 0 && P <= (int64_t)INT32_MAX, "fused_adam_step: radii must have 1 .. 2^31 - 1 entries");
+    for (torch::optim::Adam* opt : optimizers)  // before any state is touched
+        for (auto& group : opt->param_groups())
+            for (auto& p : group.params())
+                TORCH_CHECK(!p.grad().defined() || p.numel() % P == 0,
+                            "fused_adam_step: the length of radii must divide every parameter's numel()");
+    fused_adam_step_impl(optimizers, radii.data_ptr<int32_t>(), radii.numel(), guard);
 }
 
 void densify_stats(const torch::Tensor& radii, const torch::Tensor& viewspace_grad, torch::Tensor& max_radii2D,

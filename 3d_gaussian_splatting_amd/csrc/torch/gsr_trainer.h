@@ -98,6 +98,21 @@ void fused_adam_step(Map& optimizers, const RenderOutput* guard = nullptr) {  //
     for (auto& kv : optimizers) v.push_back(kv.second.get());
     fused_adam_step(static_cast<const std::vector<torch::optim::Adam*>&>(v), guard);
 }
+// The visibility-masked step (gsr_adam_step_sparse; upstream 3DGS's optimizer_type "sparse_adam"):
+// the same state handling, but only the rows of Gaussians with radii > 0 are stepped; the other
+// rows of every parameter and moment keep their bytes, and their gradients are not read.  `radii`:
+// the render's RenderOutput::radii, a contiguous int32 CUDA tensor whose length divides every
+// parameter's numel().  Every AdamParamState::step advances by one per call, visible or not, and
+// the bias corrections come from it (libtorch's, which upstream's sparse kernel does not apply),
+// so this step and opt->step() stay interchangeable on one state.
+void fused_adam_step(const std::vector<torch::optim::Adam*>& optimizers, const torch::Tensor& radii,
+                     const RenderOutput* guard = nullptr);
+template <class Map>
+void fused_adam_step(Map& optimizers, const torch::Tensor& radii, const RenderOutput* guard = nullptr) {
+    std::vector<torch::optim::Adam*> v;
+    for (auto& kv : optimizers) v.push_back(kv.second.get());
+    fused_adam_step(static_cast<const std::vector<torch::optim::Adam*>&>(v), radii, guard);
+}
 
 // Densification statistics of one render (gaussian_model.h:18-20, upstream
 // add_densification_stats): for radii > 0, max_radii2D = max(max_radii2D, radii),

@@ -55,7 +55,7 @@ EXPORTS = ["gsr_abi_version", "gsr_last_error", "gsr_forward", "gsr_read_num_ren
            "gsr_binning_bytes_aux", "gsr_image_bytes_aux", "gsr_scratch_bytes_aux"]
 # include/gsr/gsr_train.h (training-step kernels)
 TRAIN_EXPORTS = ["gsr_activate", "gsr_loss_scratch_bytes", "gsr_loss_forward", "gsr_loss_backward", "gsr_adam_step",
-                 "gsr_adam_step_guarded", "gsr_densify_stats", "gsr_densify_stats_guarded", "gsr_compact_scratch_bytes", "gsr_compact_index", "gsr_gather_rows",
+                 "gsr_adam_step_guarded", "gsr_adam_step_sparse", "gsr_densify_stats", "gsr_densify_stats_guarded", "gsr_compact_scratch_bytes", "gsr_compact_index", "gsr_gather_rows",
                  "gsr_knn_scratch_bytes", "gsr_knn_mean_dist2", "gsr_depth_loss_scratch_bytes", "gsr_depth_loss"]
 COMM_EXPORTS = ["gsr_comm_unique_id", "gsr_comm_init", "gsr_comm_destroy", "gsr_comm_size", "gsr_comm_all_to_all",
                 "gsr_comm_all_gather", "gsr_comm_all_reduce_i64"]  # include/gsr/gsr_comm.h
@@ -225,6 +225,8 @@ def load_hip() -> ctypes.CDLL:
         L.gsr_adam_step.argtypes = [ctypes.POINTER(AdamGroup), i32, f32, f32, f32, vp]
         L.gsr_adam_step_guarded.restype = ctypes.c_int
         L.gsr_adam_step_guarded.argtypes = [ctypes.POINTER(AdamGroup), i32, f32, f32, f32, vp, ctypes.c_uint32, vp]
+        L.gsr_adam_step_sparse.restype = ctypes.c_int
+        L.gsr_adam_step_sparse.argtypes = [ctypes.POINTER(AdamGroup), i32, vp, i32, f32, f32, f32, vp, ctypes.c_uint32, vp]
         L.gsr_densify_stats.restype = ctypes.c_int
         L.gsr_densify_stats.argtypes = [vp, vp, i32, vp, vp, vp, vp]
         L.gsr_densify_stats_guarded.restype = ctypes.c_int

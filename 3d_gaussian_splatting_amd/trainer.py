@@ -89,6 +89,12 @@ class OptimizationParams:
     # anti-aliased rendering (upstream's `antialiasing`; the reference's struct has none): every
     # render of step() blends the compensated opacity (gsr.h GSR_FLAG_ANTIALIAS)
     antialiasing: bool = False
+    # "default": the dense Adam step; "sparse_adam" (upstream's optimizer_type; the reference's
+    # struct has none): only the Gaussians the iteration's view rendered (radii > 0) are stepped
+    optimizer_type: str = "default"
+
+
+OPTIMIZER_TYPES = ("default", "sparse_adam")
 
 
 def _device(device) -> torch.device:
@@ -172,10 +178,21 @@ class TrainKernels:
                                           None if da is None else _p(da), _stream(self.device)), "gsr_depth_loss")
         return stats, dd, da
 
-    def adam_step(self, groups, beta1=0.9, beta2=0.999, eps=1e-8, guard=None):
+    def adam_step(self, groups, beta1=0.9, beta2=0.999, eps=1e-8, guard=None, visibility=None):
         """groups: list of dicts(param, grad, exp_avg, exp_avg_sq, act, step, lr), one launch.
         guard = (k_device, bound): the step is skipped on the device when the render's K
-        exceeded the bound it ran under (gsr_adam_step_guarded)."""
+        exceeded the bound it ran under (gsr_adam_step_guarded).
+        visibility: the rasterizer's radii, a contiguous int32 (P,) device tensor; only the rows of
+        Gaussians with radii > 0 are stepped, the others keep their bytes (gsr_adam_step_sparse)."""
+        if visibility is not None:
+            if not (visibility.is_contiguous() and visibility.dtype == torch.int32 and visibility.dim() == 1
+                    and visibility.device == self.device):
+                raise ValueError(f"adam: visibility must be a contiguous int32 (P,) tensor on {self.device}")
+            P = int(visibility.numel())
+            for g in groups:
+                n = g["param"].numel()
+                if (n % P) if P else n:
+                    raise ValueError(f"adam: a group of {n} elements is no multiple of P = {P}")
         arr = (native.AdamGroup * len(groups))()
         for i, g in enumerate(groups):
             for k in ("param", "grad", "exp_avg", "exp_avg_sq"):
@@ -190,6 +207,11 @@ class TrainKernels:
             arr[i].step = int(g["step"])
             arr[i].lr = float(g["lr"])
         gk, gcap = _guard(guard)
+        if visibility is not None:
+            self._check(self.L.gsr_adam_step_sparse(arr, len(groups), _p(visibility), P, float(beta1), float(beta2),
+                                                    float(eps), gk, gcap, _stream(self.device)),
+                        "gsr_adam_step_sparse")
+            return
         self._check(self.L.gsr_adam_step_guarded(arr, len(groups), float(beta1), float(beta2), float(eps), gk, gcap,
                                                  _stream(self.device)), "gsr_adam_step")
 
@@ -438,6 +460,8 @@ class GaussianTrainer:
 
     def setup(self, opt: OptimizationParams):
         """GaussianModel::setup (gaussian_model.cpp:316-352)."""
+        if opt.optimizer_type not in OPTIMIZER_TYPES:
+            raise ValueError(f"optimizer_type must be one of {OPTIMIZER_TYPES}, not {opt.optimizer_type!r}")
         self.opt = opt
         self.percent_dense = opt.percent_dense
         P = self.num_points
@@ -536,13 +560,16 @@ class GaussianTrainer:
                     self.binning.reset()
                     replaced.add("opacity")
         if iteration < opt.iterations:
-            self.optimizer_step({k: v for k, v in grads.items() if k not in replaced})
-        out = {"stats": stats, "radii": st.radii, "state": st, "image": st.color, "num_points": self.num_points}
+            self.optimizer_step({k: v for k, v in grads.items() if k not in replaced},
+                                visibility=st.radii if opt.optimizer_type == "sparse_adam" else None)
+        out ={"stats": stats, "radii": st.radii, "state": st, "image": st.color, "num_points": self.num_points}
         if supervised:
             out.update(depth_stats=depth_stats, depth=st.depth, alpha=st.alpha, dL_ddepth=dd)
         return out
 
-    def optimizer_step(self, grads: dict):
+    def optimizer_step(self, grads: dict, visibility: torch.Tensor | None = None):
+        """One Adam step of the groups that have a gradient; visibility (the iteration's radii):
+        only the rendered Gaussians' rows are stepped (optimizer_type "sparse_adam")."""
         groups = []
         for k in GROUPS:
             if k not in grads:
@@ -551,7 +578,9 @@ class GaussianTrainer:
             groups.append(dict(param=self.params[k], grad=grads[k].reshape(self.params[k].shape).contiguous(),
                                exp_avg=self.exp_avg[k], exp_avg_sq=self.exp_avg_sq[k], act=ACTS[k],
                                step=self.steps[k], lr=self.lr[k]))
-        if groups:
+        if groups and visibility is not None:
+            self.k.adam_step(groups, guard=self._guard, visibility=visibility)
+        elif groups:
             self.k.adam_step(groups, guard=self._guard)
 
     # ---------------------------------------------------------------- densification (upstream)

@@ -27,6 +27,8 @@
  *                             betas 0.9 / 0.999, eps 1e-8, no weight decay) stepped once each,
  *                             with the activation backward (exp / sigmoid / normalize) of
  *                             the getters fused in front of the moment update.
+ *   gsr_adam_step_sparse   <- upstream 3DGS's optimizer_type = "sparse_adam" (the reference has
+ *                             none): the same step for the Gaussians the view rendered only.
  *   gsr_densify_stats      <- max_radii2D_ / xyz_gradient_accum_ / denom_ updates
  *                             (src/scene/gaussian_model.h:18-20; setup :318-319)
  *   gsr_compact_index      <- the boolean-mask selection of prune_points / densify_and_clone
@@ -110,6 +112,22 @@ int gsr_adam_step(const gsr_adam_group* groups, int32_t ngroups, float beta1, fl
  * already advanced are not rolled back). */
 int gsr_adam_step_guarded(const gsr_adam_group* groups, int32_t ngroups, float beta1, float beta2, float eps,
                           const uint32_t* guard_k, uint32_t guard_cap, void* stream);
+/* The visibility-masked ("sparse") step: the groups are rows of n / P floats per Gaussian, and only
+ * the rows of Gaussians with radii[i] > 0 (device int32, P entries: the rasterizer's radii, the
+ * rule of gsr_densify_stats) are stepped.  A visible row is updated exactly as gsr_adam_step
+ * updates it -- same operations, same fused activation backward, bias corrections from the
+ * group's `step` -- and comes out bit-identical to it.  A row with radii[i] <= 0 keeps the bytes
+ * of param / exp_avg / exp_avg_sq and is not fetched; its grad is never used (it may hold
+ * anything, NaN included).  The groups' step counts advance once per call as for the dense
+ * step; no per-Gaussian step count is kept.  This is NOT the arithmetic of upstream 3DGS's
+ * sparse_adam optimizer: libtorch's bias correction is kept, so that the all-visible step is the
+ * dense step and the fused and the libtorch step stay interchangeable on one AdamParamState.
+ * A group with n == 0 is skipped; n % P != 0 is an error, as is a GSR_ACT_NORMALIZE4 group whose
+ * row is no multiple of 4 floats.  P == 0 or ngroups == 0: nothing to do, returns 0.  One launch,
+ * no host read, no scratch; guard_k / guard_cap as gsr_adam_step_guarded (NULL: never skipped). */
+int gsr_adam_step_sparse(const gsr_adam_group* groups, int32_t ngroups, const int32_t* radii, int32_t P,
+                         float beta1, float beta2, float eps, const uint32_t* guard_k, uint32_t guard_cap,
+                         void* stream);
 
 /* Densification statistics for the visible Gaussians (radii > 0):
  *   max_radii2D = max(max_radii2D, radii); grad_accum += |dL/dmeans2D[:, :2]|; denom += 1.
