@@ -15,6 +15,10 @@
 //                         blended depth, or depth / alpha) and dL/ddepth, dL/dalpha in the same pass:
 //                         float4 per thread, one (sum |e|, count) partial per block, summed in
 //                         double by depth_loss_finalize_kernel (fixed order, no atomics).
+//  * exposure_*_kernel    the trained per-view 3 x 4 colour transform on the render (upstream's
+//                         use_trained_exp) and its adjoint: 4 pixels of all three planes per thread,
+//                         dL/dimg and one 12-float partial of dL/dexposure per block, summed in double
+//                         by exposure_finalize_kernel (fixed order, no atomics).
 //  * adam_kernel          one launch for all six parameter groups (multi-tensor): activation
 //                         backward, moments, bias-corrected update; float4 per thread.
 //  * adam_sparse_kernel   the same step for the rows of Gaussians with radii > 0 only: a block reads
@@ -31,6 +35,7 @@
 #include <climits>
 #include <cmath>
 #include <cstring>
+#include <initializer_list>
 
 #include "../../include/gsr/gsr_train.h"
 
@@ -431,6 +436,170 @@ __global__ __launch_bounds__(256) void depth_loss_finalize_kernel(const float2* 
         stats[0] = weight * l1;
         stats[1] = l1;
         stats[2] = (float)rc[0];
+    }
+}
+
+// ---------------------------------------------------------------- per-view exposure
+// out = clamp?(x E[:3,:3] + E[:3,3]) over a channel-major 3 x H x W image (x a row vector per pixel,
+// so the 3 x 3 part is indexed E[i][j]: input channel i, output channel j), and its adjoint.  The
+// geometry is the depth loss's: a block takes chunks of 256 x 4 consecutive pixels, chunk c of
+// block b being b + c * gridDim.x, on a grid that depends on H * W alone.
+constexpr int kExpBlock = kDepthBlock, kExpChunk = kDepthChunk, kExpWaves = kExpBlock / 64;
+
+// E is the row-major 3 x 4 matrix: the one expression of y_j every path evaluates (forward, and
+// the backward's clamp mask), uncontracted, so that they round alike
+__device__ __forceinline__ float exposure_y(const float (&E)[12], int j, float x0, float x1, float x2) {
+#pragma clang fp contract(off)
+    return ((E[j] * x0 + E[4 + j] * x1) + E[8 + j] * x2) + E[4 * j + 3];
+}
+
+__device__ __forceinline__ void exposure_load_matrix(const float* __restrict__ exposure, float (&E)[12]) {
+#pragma unroll
+    for (int k = 0; k < 12; ++k) E[k] = exposure[k];
+}
+
+template <bool V4>
+__device__ __forceinline__ void exposure_forward_group(const float* img, float* out, const float (&E)[12],
+                                                       long long n, long long e0, int cnt, bool clamp) {
+    float x[3][4], y[4];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) depth_load4<V4>(img + i * n, e0, cnt, x[i]);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float v = exposure_y(E, j, x[0][k], x[1][k], x[2][k]);
+            y[k] = clamp ? fminf(fmaxf(v, 0.f), 1.f) : v;
+        }
+        depth_store4<V4>(out + j * n, e0, cnt, y);
+    }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(kExpBlock) void exposure_forward_kernel(const float* __restrict__ img,
+                                                                     const float* __restrict__ exposure, long long n,
+                                                                     int clamp, float* __restrict__ out) {
+    float E[12];
+    exposure_load_matrix(exposure, E);
+    const long long chunks = depth_loss_chunks(n);
+    for (long long c = blockIdx.x; c < chunks; c += gridDim.x) {
+        const long long e0 = c * kExpChunk + 4 * (long long)threadIdx.x;
+        const long long left = n - e0;
+        if (left <= 0) continue;
+        if (VEC && left >= 4)
+            exposure_forward_group<true>(img, out, E, n, e0, 4, clamp != 0);
+        else
+            exposure_forward_group<false>(img, out, E, n, e0, left < 4 ? (int)left : 4, clamp != 0);
+    }
+}
+
+// the pixels e0 .. e0 + cnt - 1 of one thread: dL/dimg out, the 12 sums (acc[3 i + j] = sum x_i g_j,
+// acc[9 + j] = sum g_j) into the thread's accumulators.  A lane past cnt loads x = g = 0.
+template <bool V4>
+__device__ __forceinline__ void exposure_backward_group(const float* img, const float* dout, float* dimg,
+                                                        const float (&E)[12], long long n, long long e0, int cnt,
+                                                        bool clamp, float (&acc)[12]) {
+#pragma clang fp contract(off)  // both instantiations round alike: float4 and scalar paths, same bits
+    float x[3][4], g[3][4], d[4];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        depth_load4<V4>(img + i * n, e0, cnt, x[i]);
+        depth_load4<V4>(dout + i * n, e0, cnt, g[i]);
+    }
+    if (clamp) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float v = exposure_y(E, j, x[0][k], x[1][k], x[2][k]);
+                if (v < 0.f || v > 1.f) g[j][k] = 0.f;  // inclusive bounds, as torch.clamp's backward
+            }
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) d[k] = (E[4 * i] * g[0][k] + E[4 * i + 1] * g[1][k]) + E[4 * i + 2] * g[2][k];
+        depth_store4<V4>(dimg + i * n, e0, cnt, d);
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) acc[3 * i + j] += x[i][k] * g[j][k];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) acc[9 + j] += g[j][k];
+    }
+}
+
+// one 12-float partial per block (3 float4 stores), reduced wave-then-block in a fixed order
+template <bool VEC>
+__global__ __launch_bounds__(kExpBlock) void exposure_backward_kernel(const float* __restrict__ img,
+                                                                      const float* __restrict__ exposure,
+                                                                      const float* __restrict__ dout, long long n,
+                                                                      int clamp, float* __restrict__ dimg,
+                                                                      float4* __restrict__ part) {
+    __shared__ float red[kExpWaves][12];
+    float E[12], acc[12];
+    exposure_load_matrix(exposure, E);
+#pragma unroll
+    for (int k = 0; k < 12; ++k) acc[k] = 0.f;
+    const long long chunks = depth_loss_chunks(n);
+    for (long long c = blockIdx.x; c < chunks; c += gridDim.x) {
+        const long long e0 = c * kExpChunk + 4 * (long long)threadIdx.x;
+        const long long left = n - e0;
+        if (left <= 0) continue;
+        if (VEC && left >= 4)
+            exposure_backward_group<true>(img, dout, dimg, E, n, e0, 4, clamp != 0, acc);
+        else
+            exposure_backward_group<false>(img, dout, dimg, E, n, e0, left < 4 ? (int)left : 4, clamp != 0, acc);
+    }
+#pragma unroll
+    for (int k = 0; k < 12; ++k) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) acc[k] += __shfl_xor(acc[k], o);
+    }
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < 12; ++k) red[threadIdx.x >> 6][k] = acc[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        float v[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int q = 4 * threadIdx.x + k;
+            v[k] = (red[0][q] + red[1][q]) + (red[2][q] + red[3][q]);
+        }
+        part[3 * (long long)blockIdx.x + threadIdx.x] = make_float4(v[0], v[1], v[2], v[3]);
+    }
+}
+
+// one block: the partials in double, in index order per thread and a fixed tree across threads;
+// written (not accumulated) into the 3 x 4 layout of the parameter
+__global__ __launch_bounds__(256) void exposure_finalize_kernel(const float* __restrict__ part, int nparts,
+                                                                float* __restrict__ dexposure) {
+    __shared__ double r[12][256];
+    double s[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) s[k] = 0.0;
+    for (int i = threadIdx.x; i < nparts; i += 256) {
+#pragma unroll
+        for (int k = 0; k < 12; ++k) s[k] += (double)part[12 * (long long)i + k];
+    }
+#pragma unroll
+    for (int k = 0; k < 12; ++k) r[k][threadIdx.x] = s[k];
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) {
+#pragma unroll
+            for (int k = 0; k < 12; ++k) r[k][threadIdx.x] += r[k][threadIdx.x + o];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x < 12) {
+        const int k = threadIdx.x;  // k < 9: sum x_i g_j at [i][j]; k = 9 + j: sum g_j at [j][3]
+        dexposure[k < 9 ? 4 * (k / 3) + k % 3 : 4 * (k - 9) + 3] = (float)r[k][0];
     }
 }
 
@@ -867,6 +1036,60 @@ int gsr_depth_loss(const float* depth, const float* alpha, const float* target, 
     else
         hipLaunchKernelGGL(depth_loss_kernel<false>, dim3(nb), dim3(kDepthBlock), 0, s, a, part);
     hipLaunchKernelGGL(depth_loss_finalize_kernel, dim3(1), dim3(256), 0, s, part, nb, 1.0 / (double)a.n, weight, stats);
+    return (int)hipGetLastError();
+}
+
+size_t gsr_exposure_scratch_bytes(int32_t H, int32_t W) {
+    const long long n = (long long)(H > 0 ? H : 0) * (W > 0 ? W : 0);
+    return align256((size_t)depth_loss_blocks(n) * 12 * sizeof(float));
+}
+
+// the checks both exposure passes share; 0, or < 0 with the error text set
+static int exposure_check(int32_t H, int32_t W, uint32_t flags, bool any_null) {
+    if (H <= 0 || W <= 0) return set_error(-1, "exposure: bad image shape");
+    if (any_null) return set_error(-1, "exposure: null pointer");
+    if (flags & ~(uint32_t)GSR_EXPOSURE_CLAMP) return set_error(-1, "exposure: unknown flag bits");
+    return 0;
+}
+
+// float4 accesses need every plane at 16 bytes: an aligned base and a plane of a multiple of 4 pixels
+static bool exposure_vec(long long n, std::initializer_list<const void*> images) {
+    bool vec = n % 4 == 0;
+    for (const void* p : images)
+        if (reinterpret_cast<uintptr_t>(p) & 15) vec = false;
+    return vec;
+}
+
+int gsr_exposure_forward(const float* img, const float* exposure, int32_t H, int32_t W, uint32_t flags, float* out,
+                         void* stream) {
+    if (int e = exposure_check(H, W, flags, !img || !exposure || !out)) return e;
+    const long long n = (long long)H * W;
+    const int nb = depth_loss_blocks(n), clamp = (flags & GSR_EXPOSURE_CLAMP) ? 1 : 0;
+    hipStream_t s = (hipStream_t)stream;
+    if (exposure_vec(n, {img, out}))
+        hipLaunchKernelGGL(exposure_forward_kernel<true>, dim3(nb), dim3(kExpBlock), 0, s, img, exposure, n, clamp, out);
+    else
+        hipLaunchKernelGGL(exposure_forward_kernel<false>, dim3(nb), dim3(kExpBlock), 0, s, img, exposure, n, clamp, out);
+    return (int)hipGetLastError();
+}
+
+int gsr_exposure_backward(const float* img, const float* exposure, const float* dL_dout, int32_t H, int32_t W,
+                          uint32_t flags, void* scratch, float* dL_dimg, float* dL_dexposure, void* stream) {
+    if (int e = exposure_check(H, W, flags, !img || !exposure || !dL_dout || !scratch || !dL_dimg || !dL_dexposure))
+        return e;
+    if (reinterpret_cast<uintptr_t>(scratch) & 15) return set_error(-1, "exposure: scratch must be 16-byte aligned");
+    const long long n = (long long)H * W;
+    const int nb = depth_loss_blocks(n), clamp = (flags & GSR_EXPOSURE_CLAMP) ? 1 : 0;
+    float4* part = static_cast<float4*>(scratch);
+    hipStream_t s = (hipStream_t)stream;
+    if (exposure_vec(n, {img, dL_dout, dL_dimg}))
+        hipLaunchKernelGGL(exposure_backward_kernel<true>, dim3(nb), dim3(kExpBlock), 0, s, img, exposure, dL_dout, n,
+                           clamp, dL_dimg, part);
+    else
+        hipLaunchKernelGGL(exposure_backward_kernel<false>, dim3(nb), dim3(kExpBlock), 0, s, img, exposure, dL_dout, n,
+                           clamp, dL_dimg, part);
+    hipLaunchKernelGGL(exposure_finalize_kernel, dim3(1), dim3(256), 0, s, reinterpret_cast<const float*>(part), nb,
+                       dL_dexposure);
     return (int)hipGetLastError();
 }
 

@@ -216,6 +216,10 @@ PYBIND11_MODULE(_gsr_torch, m) {
         },
         py::arg("depth"), py::arg("alpha"), py::arg("target"), py::arg("mask"), py::arg("weight") = 1.0,
         py::arg("mode") = GSR_DEPTH_RAW, py::arg("alpha_min") = 0.5);
+    m.def(
+        "apply_exposure",
+        [](torch::Tensor image, torch::Tensor exposure, bool clamp) { return gsr::apply_exposure(image, exposure, clamp); },
+        py::arg("image"), py::arg("exposure"), py::arg("clamp") = false);
     m.def("eval_sh_colors", &gsr::eval_sh_colors);
     m.def(
         "camera_from_tensors",

@@ -107,6 +107,41 @@ class DepthLoss : public torch::autograd::Function<DepthLoss> {
     }
 };
 
+// ---- per-view exposure autograd Function ----
+class ApplyExposure : public torch::autograd::Function<ApplyExposure> {
+   public:
+    static torch::Tensor forward(AutogradContext* ctx, torch::Tensor image, torch::Tensor exposure, bool clamp) {
+        TORCH_CHECK(image.dim() == 3 && image.size(0) == 3, "exposure: image must be (3,H,W)");
+        TORCH_CHECK(exposure.dim() == 2 && exposure.size(0) == 3 && exposure.size(1) == 4,
+                    "exposure: exposure must be (3,4)");
+        auto img = image.contiguous(), E = exposure.contiguous();
+        require_f32(img, "image");
+        require_f32(E, "exposure");
+        const int H = (int)img.size(1), W = (int)img.size(2);
+        auto out = torch::empty_like(img);
+        check(gsr_exposure_forward(fp(img), fp(E), H, W, clamp ? GSR_EXPOSURE_CLAMP : 0u, fp(out), stream()),
+              "gsr_exposure_forward");
+        ctx->save_for_backward({img, E});
+        ctx->saved_data["clamp"] = clamp;
+        return out;
+    }
+
+    static variable_list backward(AutogradContext* ctx, variable_list grad_out) {
+        auto sv = ctx->get_saved_variables();
+        auto img = sv[0], E = sv[1];
+        auto g = grad_out[0].contiguous();
+        require_f32(g, "exposure: the incoming gradient");
+        const int H = (int)img.size(1), W = (int)img.size(2);
+        auto scratch = torch::empty({(int64_t)gsr_exposure_scratch_bytes(H, W)}, img.options().dtype(torch::kUInt8));
+        auto dimg = torch::empty_like(img);
+        auto dE = torch::empty_like(E);
+        check(gsr_exposure_backward(fp(img), fp(E), fp(g), H, W, ctx->saved_data["clamp"].toBool() ? GSR_EXPOSURE_CLAMP : 0u,
+                                    scratch.data_ptr(), fp(dimg), fp(dE), stream()),
+              "gsr_exposure_backward");
+        return {dimg, dE, torch::Tensor()};
+    }
+};
+
 }  // namespace
 
 std::function<double(int)> get_expon_lr_func(double lr_init, double lr_final, int lr_delay_steps,
@@ -136,6 +171,10 @@ torch::Tensor depth_loss(const torch::Tensor& depth, const torch::Tensor& alpha,
                                  (int64_t)mode, alpha_min);
     if (stats) *stats = outs[1];
     return outs[0];
+}
+
+torch::Tensor apply_exposure(const torch::Tensor& image, const torch::Tensor& exposure, bool clamp) {
+    return ApplyExposure::apply(image, exposure, clamp);
 }
 
 namespace {

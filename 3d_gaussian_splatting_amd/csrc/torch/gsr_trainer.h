@@ -17,7 +17,8 @@
 //    over it reproduces the Python loop bit for bit (tests/test_gpu_train_loop.py).  It trains on
 //    colour only: depth supervision (gsr::depth_loss below, GaussianTrainer.step(gt_depth=...) in
 //    Python) is not part of Trainer::step or the gsr_train_loop executable, whose scene file
-//    carries no depth targets.
+//    carries no depth targets; nor is the trained per-view exposure (gsr::apply_exposure below,
+//    OptimizationParams.train_exposure in Python), for which the reference's struct has no switch.
 //
 // OptimizationParams is the reference's struct (src/arguments/params.h:50-91: same fields,
 // float types and defaults).
@@ -82,6 +83,14 @@ torch::Tensor photometric_loss(const torch::Tensor& image, const torch::Tensor& 
 torch::Tensor depth_loss(const torch::Tensor& depth, const torch::Tensor& alpha, const torch::Tensor& target,
                          const torch::Tensor& mask, double weight, int mode = GSR_DEPTH_RAW,
                          double alpha_min = 0.5, torch::Tensor* stats = nullptr);
+
+// The trained per-view exposure of upstream 3DGS (use_trained_exp) on a (3,H,W) render: out_j =
+// sum_i exposure[i][j] image_i + exposure[j][3], clamped to [0, 1] with `clamp`; exposure is a (3,4)
+// device tensor, e.g. one row of the (N,3,4) parameter.  An autograd Function over
+// gsr_exposure_forward / gsr_exposure_backward, differentiable in both arguments; outputs and
+// gradients are the C ABI's bits.  gsr::render's signature is the reference's and does not change:
+// a caller composes the two, gsr::apply_exposure(gsr::render(...).render, exposure[view]).  No host wait.
+torch::Tensor apply_exposure(const torch::Tensor& image, const torch::Tensor& exposure, bool clamp = false);
 
 // One step of every given torch::optim::Adam, fused into ONE gsr_adam_step launch over all
 // their parameters, on libtorch's own state (AdamParamState exp_avg / exp_avg_sq / step, created

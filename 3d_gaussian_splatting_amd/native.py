@@ -56,12 +56,14 @@ EXPORTS = ["gsr_abi_version", "gsr_last_error", "gsr_forward", "gsr_read_num_ren
 # include/gsr/gsr_train.h (training-step kernels)
 TRAIN_EXPORTS = ["gsr_activate", "gsr_loss_scratch_bytes", "gsr_loss_forward", "gsr_loss_backward", "gsr_adam_step",
                  "gsr_adam_step_guarded", "gsr_adam_step_sparse", "gsr_densify_stats", "gsr_densify_stats_guarded", "gsr_compact_scratch_bytes", "gsr_compact_index", "gsr_gather_rows",
-                 "gsr_knn_scratch_bytes", "gsr_knn_mean_dist2", "gsr_depth_loss_scratch_bytes", "gsr_depth_loss"]
+                 "gsr_knn_scratch_bytes", "gsr_knn_mean_dist2", "gsr_depth_loss_scratch_bytes", "gsr_depth_loss",
+                 "gsr_exposure_scratch_bytes", "gsr_exposure_forward", "gsr_exposure_backward"]
 COMM_EXPORTS = ["gsr_comm_unique_id", "gsr_comm_init", "gsr_comm_destroy", "gsr_comm_size", "gsr_comm_all_to_all",
                 "gsr_comm_all_gather", "gsr_comm_all_reduce_i64"]  # include/gsr/gsr_comm.h
 COMM_ID_BYTES = 128
 ACT_NONE, ACT_EXP, ACT_SIGMOID, ACT_NORMALIZE4 = range(4)
 DEPTH_RAW, DEPTH_NORMALIZED = range(2)  # gsr_train.h GSR_DEPTH_*
+EXPOSURE_CLAMP = 1  # gsr_train.h GSR_EXPOSURE_CLAMP: clamp the exposed image to [0, 1]
 ADAM_MAX_GROUPS = 8
 GATHER_MAX = 24
 STAGES = ["preprocess", "depth_sort", "scan", "duplicate", "tile_sort", "finalize", "blend_fwd", "blend_bwd",
@@ -221,6 +223,12 @@ def load_hip() -> ctypes.CDLL:
         L.gsr_depth_loss_scratch_bytes.argtypes = [i32, i32]
         L.gsr_depth_loss.restype = ctypes.c_int
         L.gsr_depth_loss.argtypes = [vp, vp, vp, vp, i32, i32, f32, i32, f32, vp, vp, vp, vp, vp]
+        L.gsr_exposure_scratch_bytes.restype = ctypes.c_size_t
+        L.gsr_exposure_scratch_bytes.argtypes = [i32, i32]
+        L.gsr_exposure_forward.restype = ctypes.c_int
+        L.gsr_exposure_forward.argtypes = [vp, vp, i32, i32, ctypes.c_uint32, vp, vp]
+        L.gsr_exposure_backward.restype = ctypes.c_int
+        L.gsr_exposure_backward.argtypes = [vp, vp, vp, i32, i32, ctypes.c_uint32, vp, vp, vp, vp]
         L.gsr_adam_step.restype = ctypes.c_int
         L.gsr_adam_step.argtypes = [ctypes.POINTER(AdamGroup), i32, f32, f32, f32, vp]
         L.gsr_adam_step_guarded.restype = ctypes.c_int

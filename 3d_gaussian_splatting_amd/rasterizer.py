@@ -616,6 +616,14 @@ def depth_loss(depth, target, mask=None, alpha=None, weight=1.0, normalized=Fals
     return (loss, stats) if return_stats else loss
 
 
+def apply_exposure(image, exposure, clamp=False):
+    """Upstream's trained per-image exposure on a (3, H, W) render: out_j = sum_i exposure[i][j]
+    image_i + exposure[j][3] (exposure: (3, 4), e.g. a row of the (N, 3, 4) parameter), clamped to
+    [0, 1] with `clamp`.  One fused HIP pass per direction (gsr_exposure_forward / _backward) behind
+    a libtorch autograd Function, differentiable in both arguments."""
+    return native.load_torch_ext().apply_exposure(image, exposure, bool(clamp))
+
+
 @dataclass
 class PipelineParams:
     """Mirror of src/arguments/params.h:93-106."""
@@ -626,12 +634,14 @@ class PipelineParams:
 
 
 def render(viewpoint_camera: RasterCamera, pc, pipe: PipelineParams, bg_color, scaling_modifier=1.0,
-           override_color=None, return_depth=False, inverse_depth=False) -> dict:
+           override_color=None, return_depth=False, inverse_depth=False, exposure=None, clamp=False) -> dict:
     """render(): same contract as the C++ gsr::render template (csrc/torch/gsr_render.h) for a
     model exposing the reference GaussianModel getters (see model.GaussianModel).  return_depth
     adds the differentiable keys "depth" (sum w z, or sum w / z with inverse_depth) and "alpha"
     (sum w); without it the dict and the kernels launched are the colour-only ones.
-    pipe.antialiasing renders with the opacity compensation (gsr.h GSR_FLAG_ANTIALIAS)."""
+    pipe.antialiasing renders with the opacity compensation (gsr.h GSR_FLAG_ANTIALIAS).
+    exposure (3, 4): upstream's use_trained_exp -- "render" is apply_exposure(render, exposure, clamp);
+    without one the dict and the kernels launched are unchanged."""
     from .general import eval_sh
     xyz = pc.get_xyz
     screenspace = torch.zeros_like(xyz, requires_grad=True)
@@ -656,7 +666,11 @@ def render(viewpoint_camera: RasterCamera, pc, pipe: PipelineParams, bg_color, s
     if return_depth:
         color, depth, alpha, radii = rasterize_gaussians_aux(viewpoint_camera, xyz, screenspace, pc.get_opacity,
                                                              inverse_depth=inverse_depth, **kw)
+        if exposure is not None:
+            color = apply_exposure(color, exposure, clamp)
         return dict(render=color, viewspace_points=screenspace, visibility_filter=radii > 0, radii=radii,
                     depth=depth, alpha=alpha)
     color, radii = rasterize_gaussians(viewpoint_camera, xyz, screenspace, pc.get_opacity, **kw)
+    if exposure is not None:
+        color = apply_exposure(color, exposure, clamp)
     return dict(render=color, viewspace_points=screenspace, visibility_filter=radii > 0, radii=radii)

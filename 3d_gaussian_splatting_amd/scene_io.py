@@ -483,7 +483,13 @@ def save_checkpoint(path: str, state: dict) -> None:
     extra = {}
     if "cameras_extent" in state:
         extra["cameras_extent"] = torch.tensor(float(state["cameras_extent"]), dtype=torch.float64)
-    torch.save({"core": core, "optim": optim, "extra": extra}, path)
+    blob = {"core": core, "optim": optim, "extra": extra}
+    ex = state.get("exposure")
+    if ex is not None:  # the per-view exposure parameter, its Adam state and the image names
+        blob["exposure"] = {"param": cpu(ex["param"]), "exp_avg": cpu(ex["exp_avg"]), "exp_avg_sq": cpu(ex["exp_avg_sq"]),
+                            "step": torch.tensor(int(ex["step"])),
+                            "names": None if ex.get("names") is None else [str(n) for n in ex["names"]]}
+    torch.save(blob, path)
 
 
 def load_checkpoint(path: str, device="cpu") -> dict:
@@ -499,6 +505,10 @@ def load_checkpoint(path: str, device="cpu") -> dict:
     st["steps"] = {k: int(v["step"].item()) for k, v in raw["optim"].items()}
     for k, v in raw.get("extra", {}).items():
         st[k] = float(v.item())
+    ex = raw.get("exposure")  # a checkpoint written without exposure has none
+    st["exposure"] = None if ex is None else {"param": ex["param"], "exp_avg": ex["exp_avg"],
+                                               "exp_avg_sq": ex["exp_avg_sq"], "step": int(ex["step"].item()),
+                                               "names": ex["names"]}
     return st
 
 
@@ -532,6 +542,34 @@ def depth_target(raw, scale: float, offset: float, med_scale: float):
     target = np.asarray(raw, np.float32) * np.float32(scale) + np.float32(offset)
     reliable = bool(0.2 * med_scale <= scale <= 5.0 * med_scale)
     return target, reliable
+
+
+# ------------------------------------------------------------------------------------------
+# trained per-view exposure (upstream 3DGS)
+# ------------------------------------------------------------------------------------------
+def save_exposures(path: str, names, exposure) -> None:
+    """Upstream's exposure.json: {image_name: 3 x 4 nested list}, one row of the (N, 3, 4) exposure
+    parameter per training image.  The f32 values are written as the doubles they equal, so
+    load_exposures returns the same bits."""
+    e = _host(exposure).astype(np.float32).reshape(-1, 3, 4)
+    names = [str(n) for n in names]
+    if len(names) != e.shape[0] or len(set(names)) != len(names):
+        raise ValueError("save_exposures: one distinct name per exposure row")
+    with open(path, "w") as fh:
+        json.dump({n: e[i].astype(np.float64).tolist() for i, n in enumerate(names)}, fh, indent=2)
+
+
+def load_exposures(path: str) -> dict[str, np.ndarray]:
+    """-> {image_name: (3, 4) f32 array} from upstream's exposure.json."""
+    with open(path) as fh:
+        raw = json.load(fh)
+    out = {}
+    for k, v in raw.items():
+        a = np.asarray(v, np.float64)
+        if a.shape != (3, 4):
+            raise ValueError(f"load_exposures: {k!r} is not a 3 x 4 matrix")
+        out[str(k)] = a.astype(np.float32)
+    return out
 
 
 def rgb2sh(rgb):

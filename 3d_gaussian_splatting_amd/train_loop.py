@@ -10,7 +10,8 @@ statistics, densify / prune every ``densification_interval`` iterations in
 then the fused Adam step -- with the OptimizationParams defaults of src/arguments/params.h:50-91.
 No host synchronisation inside an iteration except the densification read-backs; the loss is
 read back only at the log points.  A scene that carries per-view depth targets adds upstream's
-depth term to every iteration (``GaussianTrainer.step(gt_depth=...)``).
+depth term to every iteration (``GaussianTrainer.step(gt_depth=...)``); ``opt.train_exposure`` trains
+one exposure row per view beside the Gaussians (``step(view_index=...)``).
 
 The scene: ground-truth images rendered by the same rasterizer from a procedural cloud of
 Gaussians (a textured ground disc and a few object blobs, SH degree 1) seen by cameras on an
@@ -44,6 +45,7 @@ class LoopScene:
     n_gt: int = 0
     depths: list | None = None       # (H, W) f32 device tensors: per-view depth targets (inverse depth)
     depth_masks: list | None = None  # (H, W) f32 device tensors, or None for all ones
+    exposures: list | None = None    # (3, 4) arrays: the per-view colour transform the targets were made under
 
 
 def look_at_camera(center, target, fovx: float, width: int, height: int) -> graphics.RasterCamera:
@@ -115,11 +117,15 @@ def procedural_cloud(n: int, seed: int = 0, texture: float = 0.25, gt_scale: flo
 
 def synthetic_scene(n_gt: int, n_init: int, n_views: int, width: int, height: int, seed: int = 0,
                     device="cuda", texture: float = 0.25, gt_scale: float = 0.012,
-                    with_depth: bool = False) -> LoopScene:
+                    with_depth: bool = False, exposures=None) -> LoopScene:
     """Ground truth rendered once per view (the rasterizer's forward, no gradients), and a
     sparse noisy initial point cloud.  with_depth: every view also gets a depth target, the
     ground-truth cloud's blended inverse depth (forward_aux(inverse_depth=True).depth, un-normalised
-    like upstream's invDepth); the colour targets are the same with and without it."""
+    like upstream's invDepth); the colour targets are the same with and without it.  exposures: one
+    3 x 4 matrix per view, applied to that view's ground-truth image (gsr_exposure_forward, clamped to
+    [0, 1]) -- a capture with per-image exposure for opt.train_exposure to undo -- and kept on the scene."""
+    if exposures is not None and len(exposures) != n_views:
+        raise ValueError("synthetic_scene: one exposure matrix per view")
     means, f_dc, f_rest, opac, log_s, q, rgb = procedural_cloud(n_gt, seed, texture, gt_scale)
     cams = orbit_cameras(n_views, width, height, seed=seed)
     dev = torch.device(device)
@@ -133,7 +139,11 @@ def synthetic_scene(n_gt: int, n_init: int, n_views: int, width: int, height: in
         sa, qa, oa = TrainKernels(dev).activate(t(log_s), t(q), t(opac))
     for cam in cams:
         st = rast.forward(cam, t(means), op, scales=sc, rotations=qq, sh_dc=t(f_dc), sh_rest=t(f_rest), sh_degree=1)
-        gts.append(st.color.clamp(0.0, 1.0).contiguous())
+        gt = st.color.clamp(0.0, 1.0).contiguous()
+        if exposures is not None:
+            E = torch.as_tensor(np.asarray(exposures[len(gts)], np.float32).reshape(3, 4), device=dev).contiguous()
+            gt = TrainKernels(dev).exposure_forward(gt, E, clamp=True)
+        gts.append(gt)
         if with_depth:
             sd = rast.forward_aux(cam, t(means), oa.reshape(-1), scales=sa, rotations=qa, sh_dc=t(f_dc),
                                   sh_rest=t(f_rest), sh_degree=1, inverse_depth=True)
@@ -143,7 +153,8 @@ def synthetic_scene(n_gt: int, n_init: int, n_views: int, width: int, height: in
     centres = np.stack([c.campos for c in cams]).astype(np.float64)
     extent = float(np.linalg.norm(centres - centres.mean(0), axis=1).max() * 1.1)  # get_nerfpp_norm radius
     return LoopScene(cams=cams, gts=gts, points=pts.astype(np.float32), colors=rgb[pick], extent=extent, n_gt=n_gt,
-                     depths=depths if with_depth else None)
+                     depths=depths if with_depth else None,
+                     exposures=None if exposures is None else [np.asarray(e, np.float32).reshape(3, 4) for e in exposures])
 
 
 @dataclass
@@ -182,6 +193,9 @@ def write_scene(path: str, scene: LoopScene, iterations: int, opt: OptimizationP
         raise ValueError("write_scene: the GSRLOOP1 file has no depth targets (the C++ loop trains on colour only); "
                          "pass a scene without depths")
     opt = opt or OptimizationParams()
+    if opt.train_exposure:
+        raise ValueError("write_scene: the GSRLOOP1 file has no exposure switch (the C++ loop trains without "
+                         "per-view exposure); pass opt.train_exposure = False")
     views = view_sequence(len(scene.cams), iterations, seed) if views is None else np.asarray(views, np.int32)
     H, W = int(scene.gts[0].shape[1]), int(scene.gts[0].shape[2])
     with open(path, "wb") as f:
@@ -217,6 +231,8 @@ def train(scene: LoopScene, iterations: int | None = None, opt: OptimizationPara
     iterations = iterations or opt.iterations
     tr = GaussianTrainer.from_point_cloud(scene.points, scene.colors, max_sh_degree, spatial_lr_scale=scene.extent,
                                           opt=opt, device=device, seed=seed)
+    if opt.train_exposure:
+        tr.setup_exposure(len(scene.cams))
     views = view_sequence(len(scene.cams), iterations, seed)
     res = LoopResult(iterations=iterations, seconds=0.0, iters_per_s=0.0)
     logged, depth_logged = [], []
@@ -224,11 +240,12 @@ def train(scene: LoopScene, iterations: int | None = None, opt: OptimizationPara
     t0 = time.perf_counter()
     for it in range(1, iterations + 1):
         v = int(views[it - 1])
+        kw = dict(view_index=v) if opt.train_exposure else {}
         if scene.depths is not None:
             out = tr.step(it, scene.cams[v], scene.gts[v], gt_depth=scene.depths[v],
-                          depth_mask=scene.depth_masks[v] if scene.depth_masks is not None else None)
+                          depth_mask=scene.depth_masks[v] if scene.depth_masks is not None else None, **kw)
         else:
-            out = tr.step(it, scene.cams[v], scene.gts[v])
+            out = tr.step(it, scene.cams[v], scene.gts[v], **kw)
         if it % log_every == 0 or it == 1 or it == iterations:
             logged.append((it, out["stats"]))
             if "depth_stats" in out:
@@ -249,4 +266,5 @@ def train(scene: LoopScene, iterations: int | None = None, opt: OptimizationPara
     res.loss = [(it, *[float(x) for x in s.cpu().tolist()]) for it, s in logged]
     res.depth_loss = [(it, *[float(x) for x in s.cpu().tolist()]) for it, s in depth_logged]
     res.trainer = tr
+    res.last_step = out if iterations > 0 else None  # the last iteration's step() dict
     return res

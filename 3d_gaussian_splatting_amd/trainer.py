@@ -25,7 +25,9 @@ What it mirrors in the reference (seiya-kumada/3d_gaussian_splatting):
 
 Device work per iteration, all through the C ABI: gsr_activate -> gsr_forward -> loss
 forward/backward -> gsr_backward -> gsr_densify_stats -> gsr_adam_step (one launch for the
-six groups, activation backward fused); with a depth target (``step(gt_depth=...)``, upstream
+six groups, activation backward fused; with opt.train_exposure gsr_exposure_forward /
+gsr_exposure_backward around the loss and one more guarded Adam launch for the per-view exposure
+tensor); with a depth target (``step(gt_depth=...)``, upstream
 3DGS's depth regulariser -- the reference has none) the render is gsr_forward_aux /
 gsr_backward_aux with gsr_depth_loss between them.  No host synchronisation inside ``step`` (the loss
 stays on the device); densification (every ``densification_interval`` iterations) reads
@@ -92,6 +94,17 @@ class OptimizationParams:
     # "default": the dense Adam step; "sparse_adam" (upstream's optimizer_type; the reference's
     # struct has none): only the Gaussians the iteration's view rendered (radii > 0) are stepped
     optimizer_type: str = "default"
+    # trained per-view exposure (upstream's train_test_exp / use_trained_exp; the reference's struct
+    # has none): a (3, 4) affine colour transform per training image applied to the render in front
+    # of the photometric loss, with an Adam and an exponential LR schedule of its own (upstream's
+    # defaults).  exposure_clamp: the exposed image is clamped to [0, 1], as upstream's render is;
+    # it applies on the exposure path only
+    train_exposure: bool = False
+    exposure_lr_init: float = 0.01
+    exposure_lr_final: float = 0.001
+    exposure_lr_delay_steps: int = 0
+    exposure_lr_delay_mult: float = 0.0
+    exposure_clamp: bool = True
 
 
 OPTIMIZER_TYPES = ("default", "sparse_adam")
@@ -177,6 +190,47 @@ class TrainKernels:
                                           float(alpha_min), _p(scratch), _p(stats), _p(dd),
                                           None if da is None else _p(da), _stream(self.device)), "gsr_depth_loss")
         return stats, dd, da
+
+    def _exposure_args(self, what, img, exposure, extra=None):
+        if img.dim() != 3 or int(img.shape[0]) != 3:
+            raise ValueError(f"{what}: img must be (3, H, W)")
+        H, W = int(img.shape[1]), int(img.shape[2])
+        for name, t in (("img", img), ("dL_dout", extra)):
+            if t is None:
+                continue
+            if not (t.is_contiguous() and t.dtype == torch.float32 and t.device == self.device
+                    and tuple(t.shape) == (3, H, W)):
+                raise ValueError(f"{what}: {name} must be a contiguous f32 (3, {H}, {W}) tensor on {self.device}")
+        if not (exposure.is_contiguous() and exposure.dtype == torch.float32 and exposure.device == self.device
+                and tuple(exposure.shape) == (3, 4)):
+            raise ValueError(f"{what}: exposure must be a contiguous f32 (3, 4) tensor on {self.device}")
+        return H, W
+
+    def exposure_forward(self, img, exposure, clamp=False):
+        """gsr_exposure_forward: out_j = sum_i exposure[i][j] img_i + exposure[j][3] per pixel of a
+        (3, H, W) image, clamped to [0, 1] with `clamp`.  exposure: a (3, 4) device tensor, or a
+        contiguous row of the (N, 3, 4) parameter (never read by the host)."""
+        H, W = self._exposure_args("exposure_forward", img, exposure)
+        out = torch.empty_like(img)
+        self._check(self.L.gsr_exposure_forward(_p(img), _p(exposure), H, W, native.EXPOSURE_CLAMP if clamp else 0,
+                                                _p(out), _stream(self.device)), "gsr_exposure_forward")
+        return out
+
+    def exposure_backward(self, img, exposure, dL_dout, clamp=False, out=None):
+        """gsr_exposure_backward -> (dL_dimg (3, H, W), dL_dexposure (3, 4)); with `clamp` the
+        gradient is dropped where the unclamped value left [0, 1].  out: a contiguous (3, 4) f32
+        view (a row of a larger gradient tensor) that receives dL_dexposure instead of a new one."""
+        H, W = self._exposure_args("exposure_backward", img, exposure, dL_dout)
+        dE = torch.empty((3, 4), dtype=torch.float32, device=self.device) if out is None else out
+        if not (dE.is_contiguous() and dE.dtype == torch.float32 and dE.device == self.device
+                and tuple(dE.shape) == (3, 4)):
+            raise ValueError(f"exposure_backward: out must be a contiguous f32 (3, 4) tensor on {self.device}")
+        scratch = torch.empty(int(self.L.gsr_exposure_scratch_bytes(H, W)), dtype=torch.uint8, device=self.device)
+        dimg = torch.empty_like(img)
+        self._check(self.L.gsr_exposure_backward(_p(img), _p(exposure), _p(dL_dout), H, W,
+                                                 native.EXPOSURE_CLAMP if clamp else 0, _p(scratch), _p(dimg),
+                                                 _p(dE), _stream(self.device)), "gsr_exposure_backward")
+        return dimg, dE
 
     def adam_step(self, groups, beta1=0.9, beta2=0.999, eps=1e-8, guard=None, visibility=None):
         """groups: list of dicts(param, grad, exp_avg, exp_avg_sq, act, step, lr), one launch.
@@ -390,6 +444,8 @@ class GaussianTrainer:
         self.gen = torch.Generator(device=dev)
         self.gen.manual_seed(seed)
         self.binning = BinningCapacity(dev)
+        self.exposure = None  # (N, 3, 4) after setup_exposure
+        self.exposure_names = None
         self.setup(opt or OptimizationParams())
 
     @classmethod
@@ -421,7 +477,10 @@ class GaussianTrainer:
         scene_io.save_checkpoint(path, {
             "active_sh_degree": self.active_sh_degree, "spatial_lr_scale": self.spatial_lr_scale,
             "cameras_extent": self.cameras_extent, "params": self.params, "max_radii2D": self.max_radii2D, "xyz_gradient_accum": self.xyz_gradient_accum,
-            "denom": self.denom, "exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq, "steps": self.steps})
+            "denom": self.denom, "exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq, "steps": self.steps,
+            "exposure": None if self.exposure is None else {
+                "param": self.exposure, "exp_avg": self.exposure_exp_avg, "exp_avg_sq": self.exposure_exp_avg_sq,
+                "step": self.exposure_step, "names": self.exposure_names}})
 
     def restore(self, path: str, opt: OptimizationParams | None = None) -> None:
         """GaussianModel::restore (gaussian_model.cpp:248-267): setup(opt), then the captured
@@ -438,6 +497,12 @@ class GaussianTrainer:
                 self.exp_avg[k] = st["exp_avg"][k].contiguous()
                 self.exp_avg_sq[k] = st["exp_avg_sq"][k].contiguous()
                 self.steps[k] = st["steps"][k]
+        ex = st.get("exposure")  # absent in a checkpoint without exposure: it stays unset
+        self.exposure = self.exposure_names = None
+        if ex is not None:
+            self.exposure = ex["param"].contiguous()
+            self.exposure_exp_avg, self.exposure_exp_avg_sq = ex["exp_avg"].contiguous(), ex["exp_avg_sq"].contiguous()
+            self.exposure_step, self.exposure_names = ex["step"], ex["names"]
 
     def save_ply(self, path: str) -> None:
         """The raw leaves in the upstream point-cloud PLY layout (scene_io.save_gaussians_ply)."""
@@ -480,10 +545,40 @@ class GaussianTrainer:
         # upstream: depth_l1_weight = get_expon_lr_func(init, final, max_steps=opt.iterations)
         self.depth_weight_scheduler = get_expon_lr_func(opt.depth_l1_weight_init, opt.depth_l1_weight_final,
                                                         max_steps=opt.iterations)
+        # upstream: exposure_scheduler_args = get_expon_lr_func(exposure_lr_init, exposure_lr_final,
+        # lr_delay_steps, lr_delay_mult, max_steps = iterations)
+        self.exposure_scheduler = get_expon_lr_func(opt.exposure_lr_init, opt.exposure_lr_final,
+                                                    lr_delay_steps=opt.exposure_lr_delay_steps,
+                                                    lr_delay_mult=opt.exposure_lr_delay_mult,
+                                                    max_steps=opt.iterations)
+        self.exposure_lr = opt.exposure_lr_init
+
+    def setup_exposure(self, n_views: int, names=None):
+        """Upstream's per-image exposure parameter: (N, 3, 4), every row eye(3, 4), with zero Adam
+        moments and a step count of 0.  names (one per view) are kept for exposure.json."""
+        n_views = int(n_views)
+        if n_views <= 0:
+            raise ValueError("setup_exposure: n_views must be positive")
+        if names is not None and len(names) != n_views:
+            raise ValueError("setup_exposure: one name per view")
+        eye = torch.eye(3, 4, dtype=torch.float32, device=self.device)
+        self.exposure = eye[None].repeat(n_views, 1, 1).contiguous()
+        self.exposure_exp_avg = torch.zeros_like(self.exposure)
+        self.exposure_exp_avg_sq = torch.zeros_like(self.exposure)
+        self.exposure_step = 0
+        self.exposure_names = None if names is None else [str(n) for n in names]
+
+    def save_exposures(self, path: str) -> None:
+        """exposure.json in upstream's layout (scene_io.save_exposures); unnamed views are "0", "1", ..."""
+        if self.exposure is None:
+            raise ValueError("save_exposures: setup_exposure was never called")
+        names = self.exposure_names or [str(i) for i in range(int(self.exposure.shape[0]))]
+        scene_io.save_exposures(path, names, self.exposure)
 
     def update_learning_rate(self, iteration: int) -> float:
         lr = self.xyz_scheduler(iteration)
         self.lr["xyz"] = lr
+        self.exposure_lr = self.exposure_scheduler(iteration)
         return lr
 
     def oneup_SH_degree(self):
@@ -509,7 +604,8 @@ class GaussianTrainer:
         return st
 
     def step(self, iteration: int, cam, gt_image: torch.Tensor, bg=(0.0, 0.0, 0.0), densify: bool = True,
-             gt_depth: torch.Tensor | None = None, depth_mask: torch.Tensor | None = None) -> dict:
+             gt_depth: torch.Tensor | None = None, depth_mask: torch.Tensor | None = None,
+             view_index: int | None = None) -> dict:
         """One training iteration in the upstream order (train_utils.cpp:128-145 plus the body
         its stub omits): LR update, SH degree, render, loss, backward, densification statistics,
         densify / prune and opacity reset, then the optimizer step.  As upstream, a group whose
@@ -524,16 +620,44 @@ class GaussianTrainer:
         render is then forward_aux / backward_aux, pred the blended inverse depth (opt.depth_inverse;
         divided by alpha with opt.depth_normalized), and the dict gains "depth_stats" ([weighted
         loss, mean |e|, contributing pixels], device), "depth", "alpha" and "dL_ddepth".  Without a
-        target, or at a scheduled weight of 0, the iteration is the colour-only one, call for call."""
+        target, or at a scheduled weight of 0, the iteration is the colour-only one, call for call.
+
+        With opt.train_exposure, view_index names the row of the (N, 3, 4) exposure parameter
+        (setup_exposure) that belongs to this image: the loss sees gsr_exposure_forward of the render
+        (clamped with opt.exposure_clamp), gsr_exposure_backward turns its gradient into the
+        rasterizer's dL/dimage and the row's gradient, and the WHOLE exposure tensor takes one Adam
+        step with a gradient that is zero outside that row (upstream's exposure_optimizer: the other
+        rows keep moving on their decaying moments).  The dict gains "exposed" (the image the loss
+        saw) and "dL_dexposure" (3, 4); "image" stays the raw render.  Without it the iteration is
+        unchanged, call for call."""
         opt = self.opt
+        exposed = opt.train_exposure
+        if exposed:
+            if self.exposure is None:
+                raise ValueError("step: train_exposure needs setup_exposure(n_views) first")
+            if view_index is None:
+                raise ValueError("step: train_exposure needs the view_index of this image's exposure row")
+            view_index = int(view_index)
+            if not 0 <= view_index < int(self.exposure.shape[0]):
+                raise ValueError(f"step: view_index {view_index} is outside the {int(self.exposure.shape[0])} "
+                                 "exposure rows")
         self.update_learning_rate(iteration)
         if iteration % 1000 == 0:
             self.oneup_SH_degree()
         depth_weight = self.depth_weight_scheduler(iteration) if gt_depth is not None else 0.0
         supervised = depth_weight > 0.0
         st = self.render(cam, bg, aux=supervised)
-        stats, maps = self.k.loss_forward(st.color, gt_image, opt.lambda_dssim)
-        dimg = self.k.loss_backward(st.color, gt_image, opt.lambda_dssim, maps)
+        if exposed:
+            E = self.exposure[view_index]
+            image = self.k.exposure_forward(st.color, E, clamp=opt.exposure_clamp)
+            stats, maps = self.k.loss_forward(image, gt_image, opt.lambda_dssim)
+            dexposed = self.k.loss_backward(image, gt_image, opt.lambda_dssim, maps)
+            exposure_grad = torch.zeros_like(self.exposure)  # zero outside this view's row
+            dimg, dE = self.k.exposure_backward(st.color, E, dexposed, clamp=opt.exposure_clamp,
+                                                out=exposure_grad[view_index])
+        else:
+            stats, maps = self.k.loss_forward(st.color, gt_image, opt.lambda_dssim)
+            dimg = self.k.loss_backward(st.color, gt_image, opt.lambda_dssim, maps)
         if supervised:
             depth_stats, dd, da = self.k.depth_loss(st.depth, gt_depth, mask=depth_mask, alpha=st.alpha,
                                                     weight=depth_weight, normalized=opt.depth_normalized,
@@ -562,9 +686,16 @@ class GaussianTrainer:
         if iteration < opt.iterations:
             self.optimizer_step({k: v for k, v in grads.items() if k not in replaced},
                                 visibility=st.radii if opt.optimizer_type == "sparse_adam" else None)
+            if exposed:  # never replaced by densification: stepped on densify iterations too
+                self.exposure_step += 1
+                self.k.adam_step([dict(param=self.exposure, grad=exposure_grad, exp_avg=self.exposure_exp_avg,
+                                       exp_avg_sq=self.exposure_exp_avg_sq, act=native.ACT_NONE,
+                                       step=self.exposure_step, lr=self.exposure_lr)], guard=self._guard)
         out ={"stats": stats, "radii": st.radii, "state": st, "image": st.color, "num_points": self.num_points}
         if supervised:
             out.update(depth_stats=depth_stats, depth=st.depth, alpha=st.alpha, dL_ddepth=dd)
+        if exposed:
+            out.update(exposed=image, dL_dexposure=dE)
         return out
 
     def optimizer_step(self, grads: dict, visibility: torch.Tensor | None = None):

@@ -22,6 +22,11 @@
  *                             (gsr_forward_aux of gsr.h), value and gradients in one pass.  The
  *                             reference has no depth term; the normalised mode (depth / alpha)
  *                             is this project's addition.
+ *   gsr_exposure_scratch_bytes <- upstream 3DGS's trained per-image exposure (gaussian_renderer/
+ *   gsr_exposure_forward         __init__.py, use_trained_exp: matmul(image.permute(1,2,0),
+ *   gsr_exposure_backward        exposure[:3,:3]).permute(2,0,1) + exposure[:3,3,None,None]) and the
+ *                             backward autograd derives from it, one fused pass per direction.  The
+ *                             reference has none.
  *   gsr_adam_step          <- the six torch::optim::Adam instances of GaussianModel::setup
  *                             (src/scene/gaussian_model.cpp:323-345: default AdamOptions,
  *                             betas 0.9 / 0.999, eps 1e-8, no weight decay) stepped once each,
@@ -80,6 +85,28 @@ size_t gsr_depth_loss_scratch_bytes(int32_t H, int32_t W);
 int gsr_depth_loss(const float* depth, const float* alpha, const float* target, const float* mask,
                    int32_t H, int32_t W, float weight, int32_t mode, float alpha_min,
                    void* scratch, float* stats, float* dL_ddepth, float* dL_dalpha, void* stream);
+
+/* Per-view exposure: a 3 x 4 affine colour transform E (row-major, 12 DEVICE floats -- one row of
+ * upstream's (N, 3, 4) parameter; it is a trained value and the host never reads it) applied to a
+ * channel-major 3 x H x W image.  The 3 x 3 part multiplies the pixel as a ROW vector, so for output
+ * channel j:
+ *   y_j = E[0][j] x_0 + E[1][j] x_1 + E[2][j] x_2 + E[j][3]          (E[i][j], not E[j][i])
+ *   out_j = y_j, or min(max(y_j, 0), 1) with GSR_EXPOSURE_CLAMP.
+ * Backward, with g_j = dL_dout_j, and with the flag g_j = 0 where y_j < 0 or y_j > 1 (the bounds
+ * are inclusive, as in torch.clamp: the gradient passes where y_j is exactly 0 or 1):
+ *   dL_dimg_i = sum_j E[i][j] g_j;  dL_dexposure[i][j] = sum_p x_i g_j;  dL_dexposure[j][3] = sum_p g_j.
+ * dL_dexposure (12 floats, may point into a larger gradient tensor) is WRITTEN, not accumulated.
+ * The backward recomputes y with the forward's expression, so its mask is the forward's clamp.
+ * Images: any 4-byte-aligned pointer (float4 accesses when every plane is 16-byte aligned).
+ * scratch: gsr_exposure_scratch_bytes(H, W) bytes, 16-byte aligned.  The buffers must not overlap
+ * (not checked).  One pass per direction plus a one-block finalize; deterministic (fixed-order
+ * sums on a grid that depends on H * W alone, no atomics). */
+#define GSR_EXPOSURE_CLAMP 1u   /* out = min(max(y, 0), 1) after the affine map (upstream's render clamps) */
+size_t gsr_exposure_scratch_bytes(int32_t H, int32_t W);
+int gsr_exposure_forward(const float* img, const float* exposure, int32_t H, int32_t W, uint32_t flags,
+                         float* out, void* stream);
+int gsr_exposure_backward(const float* img, const float* exposure, const float* dL_dout, int32_t H, int32_t W,
+                          uint32_t flags, void* scratch, float* dL_dimg, float* dL_dexposure, void* stream);
 
 /* Activation applied by the getter in front of a parameter group (its gradient arrives with
  * respect to the activated value; gsr_adam_step converts it to the raw leaf first). */
