@@ -451,7 +451,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 2
     float* const fT = final_T + (size_t)view * npix;
 #pragma unroll
     for (int p = 0; p < PPL; ++p) {
-        const int pyl = tyl * kTile + (lane >> 4) + 4 * (w * PPL + p);
+        // the row back from its float (exact: a small integer), so that the integer does not stay
+        // live through the visit loop -- with it live, the 64-VGPR cap of kF6Wpe has pfy[0]
+        // converted again on every visit
+        const int pyl = (int)pfy[p];
         if (px < geo.W && pyl < geo.vh) {
             const size_t pix = (size_t)pyl * geo.W + px;
             const float Tf = fabsf(T[p]);
@@ -471,43 +474,111 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 2
     }
 }
 
+// A record as B1 stages it in LDS: the 9 floats its record loop reads (kStagedRec floats a row)
+constexpr int kStagedRec = 10;
+struct StagedRec {
+    float4 r0;  // mean x, y, conic a (scaled), b
+    float4 h;   // r1.x, r1.z, r1.w, r2.x
+    float L;    // r2.w
+};
+__device__ __forceinline__ StagedRec staged(const float2* srec, int k) {
+    const float2* p = srec + k * (kStagedRec / 2);
+    const float2 a = p[0], b = p[1], c = p[2], d = p[3];
+    return {make_float4(a.x, a.y, b.x, b.y), make_float4(c.x, c.y, d.x, d.y), p[4].x};
+}
+
 // Deferred B1 reduction.  A record's 9 per-lane moments are quad-reduced by DPP; the 16 quad
 // partials wait in LDS, and every kPark records one (record, moment) output per lane is summed
-// from LDS in fixed quad order and stored straight to the partial arrays at the record's
-// emission index j (8 moments in part8[2j..2j+1], the 9th in part1[j]).
+// from LDS in fixed quad order (four chains over quad & 3, then (t0 + t1) + (t2 + t3): the sum
+// does not depend on kPark or on which lane takes it) and stored straight to the partial arrays
+// at the record's emission index j (8 moments in part8[2j..2j+1], the 9th in part1[j]).
+// Depth 4: at 5 (one more slot, 6,640 B of LDS) the flush's share of a record falls from 5.3 to
+// 4.2 VALU, but B1 loses the occupancy it has at 5,760 B and is slower (0.4485 vs 0.4268 ms at
+// 1M / 1080p).
 constexpr int kPark = 4;
 // Parking slot stride and the flush's lane map.  The flush reads with ds_read_b32, whose banks
 // are (address / 4) mod 32 over lane groups {0-31}, {32-63} (MI355X_MICROARCH.md, LDS table).
-// Flush lane l sums moment c = l >> 2 of parked slot s = l & 3 (36 lanes: c < 9), so lanes 0-31
-// are (c 0-7) x (s 0-3) and read word 8 s + c + 12 i (mod 32) for quad i: 32 distinct banks when
-// the slot stride is 8 mod 32 (200 = 16 quads x 12 floats + 8, 16-B aligned for the leaders'
-// float4 stores).  Round 4's map (s = l / 9, c = l mod 9, stride 204 = 12 mod 32) put slots 2 / 3
-// on slot 0's banks: a 2-way conflict on every flush read, the ~9.5e6 SQ_LDS_BANK_CONFLICT cycles
-// per launch of profiles/r04_pmc_summary.txt (16 reads x ~6.3e5 flushes at 1M / 1080p).
-constexpr int kParkSlot = 16 * 12 + 8;
-static_assert(kParkSlot % 32 == 8 && kParkSlot % 4 == 0, "flush banks / float4 alignment");
+// The flush lane of (slot s, moment c) reads word s kParkSlot + c + 12 i for quad i, so within a
+// lane group the words s kParkSlot + c must differ mod 32.  The stride is a multiple of 4 (the
+// leaders' float4 stores), so slot s covers the 9 (aux: 10) banks from 4 (m s mod 8), m =
+// kParkSlot / 4: three slots that start 4 and 8 banks apart put three lanes on one bank, which two
+// lane groups cannot separate.  Four slots take m = 2 (starts 0, 8, 16, 24: stride 200 = 16 quads
+// x 12 floats + 8); five take m = 3 (starts 0, 12, 24, 4, 16: stride 204), every bank under at
+// most two slots; 6 or 7 slots always hold such a triple, so this row allows no more than 5.
+// make_flush_map deals the (slot, moment) pairs to the two lane groups, first fit by bank, and the
+// static assertions hold the result to the rule: no two lanes of a group on one bank.
+// Round 4's map (s = l / 9, c = l mod 9, stride 204) ignored the groups and put slots 2 / 3 on
+// slot 0's banks: a 2-way conflict on every flush read, the ~9.5e6 SQ_LDS_BANK_CONFLICT cycles per
+// launch of profiles/r04_pmc_summary.txt (16 reads x ~6.3e5 flushes at 1M / 1080p).
+constexpr int kParkSlot = 16 * 12 + (kPark <= 4 ? 8 : 12);
+static_assert(kPark <= 5 && kParkSlot % 4 == 0, "flush banks / float4 alignment of the leaders' stores");
+struct FlushMap {
+    uint8_t sc[64];  // per flush lane: slot << 4 | moment, 0xFF for an idle lane
+    bool ok;
+};
+constexpr FlushMap make_flush_map(int moments) {
+    FlushMap m{};
+    for (int l = 0; l < 64; ++l) m.sc[l] = 0xFF;
+    m.ok = true;
+    bool used[2][32] = {};
+    int fill[2] = {0, 0};
+    for (int s = 0; s < kPark; ++s)
+        for (int c = 0; c < moments; ++c) {
+            const int bank = (s * kParkSlot + c) % 32;
+            const int g = used[0][bank] ? 1 : 0;
+            if (used[g][bank] || fill[g] == 32) {
+                m.ok = false;
+                continue;
+            }
+            used[g][bank] = true;
+            m.sc[32 * g + fill[g]++] = (uint8_t)(s << 4 | c);
+        }
+    return m;
+}
+__device__ constexpr FlushMap kFlushMap = make_flush_map(9), kFlushMapAux = make_flush_map(10);
+static_assert(kFlushMap.ok && kFlushMapAux.ok, "flush lanes of one group on one LDS bank");
 // The parked records' batch indices ride in one scalar word (6 bits per slot: `kpack`); the
-// flush lane of slot s reads its record's emission index from the batch's jl table (`sjl`,
-// written once per batch), so a record costs no per-record readlane / LDS write for it.
-// AUX: a tenth moment (row slot 9, flush lanes 36-39: the second ds_read_b32 lane group, whose
-// banks 8 s + 9 + 12 i are distinct as well) goes to its own per-entry array pz.
+// flush lane of slot s reads its record's emission index from the record's staged row (its tenth
+// word, written once per batch), so a record costs no per-record readlane / LDS write for it.
+static_assert(6 * kPark <= 32, "kpack");
+// AUX: a tenth moment (row slot 9) goes to its own per-entry array pz.
+// A flush lane's slot, moment and destination are fixed for the whole kernel (FlushLane, set at
+// kernel start): the LDS address of its first quad partial, and a base and byte step into its
+// moment's home array (part8 + c floats and 32 B per entry for c < 8, part1 or pz and 4 B
+// otherwise), so an entry's address is one multiply-add from j per flush.
+typedef const __attribute__((address_space(3))) float* LdsFloats;
+struct FlushLane {
+    // qpark + slot * kParkSlot + moment, as an LDS address the compiler cannot see into: the 16
+    // reads are then immediate offsets from this one register (from qpark's known offset in the
+    // LDS block it derives up to three bases, an add each per flush)
+    LdsFloats q;
+    char* base;
+    uint32_t step;
+    int slot;        // kPark for an idle lane: never below `parked`
+    bool flag;       // moment 8 sets the entry's flag byte
+};
 template <bool AUX = false>
-__device__ __forceinline__ void park_flush(const float* qpark, const uint32_t* sjl, uint32_t kpack, int parked,
-                                           float* p8f, float* p1, uint8_t* fl, int lane, float* pz = nullptr) {
+__device__ __forceinline__ FlushLane flush_lane(int lane, const float* qpark, float* p8f, float* p1, float* pz) {
+    const int sc = AUX ? kFlushMapAux.sc[lane] : kFlushMap.sc[lane];
+    const int c = sc & 15, slot = sc == 0xFF ? kPark : sc >> 4;
+    float* b = c < 8 ? p8f + c : p1;
+    if constexpr (AUX) b = c == 9 ? pz : b;
+    LdsFloats q = (LdsFloats)(qpark + (sc == 0xFF ? 0 : slot * kParkSlot + c));
+    asm volatile("" : "+v"(q));
+    return {q, reinterpret_cast<char*>(b), c < 8 ? 32u : 4u, slot, c == 8};
+}
+__device__ __forceinline__ void park_flush(const FlushLane f, const float2* srec, uint32_t kpack, int parked,
+                                           uint8_t* fl) {
     __syncthreads();  // one-wave block: orders the quad leaders' LDS writes before the reads
-    const int slot = lane & 3, c = lane >> 2;
-    if (c < (AUX ? 10 : 9) && slot < parked) {
-        const float* q = qpark + slot * kParkSlot + c;
+    if (f.slot < parked) {
         // -0 is the identity of IEEE addition, so the first add of each chain folds into a move
         float t[4] = {-0.f, -0.f, -0.f, -0.f};
 #pragma unroll
-        for (int i = 0; i < 16; ++i) t[i & 3] += q[i * 12];
-        const uint32_t j = sjl[(kpack >> (6 * slot)) & 63u];
+        for (int i = 0; i < 16; ++i) t[i & 3] += f.q[i * 12];
+        const uint32_t j = __float_as_uint(srec[((kpack >> (6 * f.slot)) & 63u) * (kStagedRec / 2) + 4].y);
         if (j != 0xFFFFFFFFu) {  // an entry past the capacity (binning overflow) has none
-            float* dst = c < 8 ? p8f + 8 * (size_t)j + c : p1 + j;
-            if constexpr (AUX) dst = c == 9 ? pz + j : dst;
-            *dst = (t[0] + t[1]) + (t[2] + t[3]);
-            if (c == 8) fl[j] = 1;  // the gather reads flagged entries only
+            *reinterpret_cast<float*>(f.base + (size_t)j * f.step) = (t[0] + t[1]) + (t[2] + t[3]);
+            if (f.flag) fl[j] = 1;  // the gather reads flagged entries only
         }
     }
     __syncthreads();
@@ -537,8 +608,15 @@ __device__ __forceinline__ void park_flush(const float* qpark, const uint32_t* s
 // says and resumes from F6's checkpoint, and slots the tile has no chunk for exit at once.  Each
 // XCD (blocks b with equal b % 8) takes a contiguous tile range as in xcd_tile, visited
 // chunk-major, so every tile's first chunk is dispatched first.
-// 6 waves per SIMD: 80 VGPRs (no spills) and 6.2 KB of LDS per one-wave block.  Measured
-// 0.552 ms vs 0.564 at the compiler's own 85 VGPRs (5 waves); 7 and 8 waves spill.
+// 6 waves per SIMD: 78 VGPRs (no spills) and 5,760 B of LDS per one-wave block (2,560 staged
+// records + 3,200 parking; the aux form's svz makes it 6,016 B, under its own 5-wave cap).
+// Rounds 4 and 6 had let the block grow to 7,296 B with three batch tables: 22 blocks per 160-KiB
+// CU, 5.5 waves per SIMD, not the 6 the registers allow.  The tables now share the parking area's
+// bytes, the staged record lost the three floats the loop never reads, and the emission index took
+// the row's spare word.  6,528 B (the shared tables alone) did not bring the occupancy back,
+// 5,760 B did: B1 0.447 against 0.427 ms with the same instructions, so
+// the block must stay well under 160 KiB / 24.  Measured (round 1) 0.552 ms vs 0.564 at the
+// compiler's own 85 VGPRs (5 waves); 7 and 8 waves spill.
 // kB1Win (gsr_internal.h) mask bytes per lane in one batch window: 256 entries per window.  B1
 // loads the window's gids with its mask bytes (one 16-B load per lane), so a batch's record
 // loads do not wait on a gid load first.
@@ -572,17 +650,25 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PF ? 4 : (si
     const B1Aux ax = aux_arg<B1Aux>(axp...);
     __shared__ float svz[AUX ? 64 : 1];  // aux: the batch's v_i (unused, so absent, otherwise)
     // One block of LDS with srec first: the record fields then sit within the immediate offsets
-    // of the record reads (8-bit dword offsets of ds_read2), so a record costs no address add.
+    // of the record reads (8-bit offsets of ds_read2), so a record costs no address add.  A staged
+    // record is the 9 floats the record loop reads in a 40-B row (8-B aligned for ds_read2_b64):
+    // r0, then (r1.x, r1.z, r1.w, r2.x), then r2.w -- not the 12 of the global record -- and in the
+    // row's tenth word the entry's emission index, which the flush lanes read by batch slot.
     __shared__ struct {
-        float4 srec[64 * 3];
-        uint32_t sjl[64];                  // the batch's emission indices, by batch slot
-        float qpark[kPark * kParkSlot];    // [slot][quad][9 of 12]
-        uint32_t sidx[64];                 // the batch's entries (list offsets), in list order
-        uint32_t smv[64];                  // and their stripe masks
-        uint32_t sgd[64];                  // and their gids (loaded with the window's mask bytes)
+        float2 srec[64 * kStagedRec / 2];
+        // The batch selection's tables share qpark's bytes: they are written and read back before
+        // the batch's first record is parked, and rewritten after its last flush (one wave, whose
+        // LDS operations complete in program order)
+        union {
+            float qpark[kPark * kParkSlot];  // [slot][quad][9 of 12]
+            struct {
+                uint32_t sidx[64];           // the batch's entries (list offsets), in list order
+                uint32_t smv[64];            // and their stripe masks
+                uint32_t sgd[64];            // and their gids (loaded with the window's mask bytes)
+            };
+        };
     } lds;
-    float4* const srec = lds.srec;
-    uint32_t* const sjl = lds.sjl;
+    float2* const srec = lds.srec;
     float* const qpark = lds.qpark;
     const int lane = threadIdx.x;
     float* const qlane = qpark + (lane >> 2) * 12;  // this quad's parking row
@@ -693,6 +779,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PF ? 4 : (si
     // F6 wrote the stripe mask of every entry it loaded, all before its termination index tend;
     // past tend no pixel is live
     const int n_lim = n < (int)tend ? n : (int)tend;
+    const FlushLane flane = flush_lane<AUX>(lane, qpark, p8f, p1, ax.pz);
     for (int base = start; base < n_lim;) {
         uint32_t live = 0;  // in stripe positions (the mask bytes' bits)
 #pragma unroll
@@ -756,20 +843,24 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PF ? 4 : (si
             // positions, not emission indices, below it) -- the entry is not written
             if (jl >= geo.cap) jl = 0xFFFFFFFFu;
             const float4* r = rec + 3 * (size_t)g;
-            srec[3 * lane + 0] = r[0];
-            srec[3 * lane + 1] = r[1];
-            srec[3 * lane + 2] = r[2];
+            const float4 r0 = r[0], r1 = r[1], r2 = r[2];
+            float2* const d = srec + lane * (kStagedRec / 2);
+            d[0] = make_float2(r0.x, r0.y);
+            d[1] = make_float2(r0.z, r0.w);
+            d[2] = make_float2(r1.x, r1.z);
+            d[3] = make_float2(r1.w, r2.x);
+            d[4] = make_float2(r2.w, __uint_as_float(jl));
             if constexpr (AUX) svz[lane] = aux_value(ax.depth_key[g], ax.inv) - vref;
             smask = lds.smv[lane];
         }
-        sjl[lane] = jl;
         __syncthreads();
         uint64_t todo = __ballot(lane < cnt);
         int visited = 0, parked = 0;
         uint32_t kpack = 0;  // batch slots of the parked records, 6 bits each
         // one visited record (batch slot k): its stripes, then its moments parked / flushed;
         // true when every pixel of the tile has finished
-        auto record = [&](const int k, const float4 r0, const float4 r1, const float4 r2, const float vz) -> bool {
+        auto record = [&](const int k, const StagedRec sr, const float vz) -> bool {
+            const float4 r0 = sr.r0, r1 = make_float4(sr.h.x, 0.0f, sr.h.y, sr.h.z), r2 = make_float4(sr.h.w, 0.0f, 0.0f, sr.L);
             const uint32_t m = (uint32_t)__builtin_amdgcn_readlane((int)smask, k) & live;
             const float dx = r0.x - pfx;
             const float bdx = r0.w * dx;
@@ -779,10 +870,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PF ? 4 : (si
             // without fast-math; +0 would keep them (0 + -0 = +0)
             float s0 = -0.f, sy = -0.f, syy = -0.f, g0 = -0.f, g1 = -0.f, g2 = -0.f;
             float gz = -0.f;  // aux: sum w dL/ddepth
-            bool any = false;
+            // lanes with a contributing pair in any stripe: the stripes' own exec masks, ORed on
+            // the scalar port (a per-lane flag costs a VGPR, a move per contributing stripe and a
+            // compare per record)
+            uint64_t any = 0;
             // one contributing (pixel, record) pair of stripe p into the record's moments
             auto contribute = [&](const int p, const float a, const float w, const float oG, const float dy) {
-                any = true;
                 const float one_m = 1.0f - a;
                 float cdp = fmaf(r1.z, dp0[p], fmaf(r1.w, dp1[p], r2.x * dp2[p]));
                 if constexpr (AUX) {
@@ -811,10 +904,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PF ? 4 : (si
                 const float w = a * T[p];
                 const float tT = T[p] - w;
                 const bool ok = tT >= 0.0001f;
+                // keep's two compares and ok's, each balloted on its own: the ballot of a compare is
+                // the compare's SGPR mask, the ballot of their conjunction a select and a compare
+                any |= __builtin_amdgcn_fcmpf(tT, 0.0001f, 3) & __builtin_amdgcn_fcmpf(e, r2.w, 5) &
+                       __builtin_amdgcn_fcmpf(oG, 1.0f / 255.0f, 3);
                 if (ok && keep) contribute(p, a, w, oG, dy);
                 T[p] = ok ? tT : -fabsf(T[p]);
             }
-            if (__any(any)) {
+            if (any) {
                 // the quad shares dx: reduce the six column sums (12 DPP adds, not 18 for the
                 // nine dx-weighted moments of a row-major quad), then apply dx once
                 float u[AUX ? 7 : 6] = {s0, sy, syy, g0, g1, g2};
@@ -831,7 +928,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PF ? 4 : (si
                 }
                 kpack |= (uint32_t)k << (6 * parked);
                 if (++parked == kPark) {
-                    park_flush<AUX>(qpark, sjl, kpack, parked, p8f, p1, fl, lane, ax.pz);
+                    park_flush(flane, srec, kpack, kPark, fl);
                     parked = 0;
                     kpack = 0;
                 }
@@ -849,29 +946,24 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PF ? 4 : (si
             if (todo) {
                 int ka = __builtin_ctzll(todo);
                 todo &= todo - 1;
-                float4 a0 = srec[3 * ka + 0], a1 = srec[3 * ka + 1], a2 = srec[3 * ka + 2];
-                float4 b0, b1, b2;
+                StagedRec ra = staged(srec, ka), rb;
                 float za = 0.0f, zb = 0.0f;
                 if constexpr (AUX) za = svz[ka];
                 while (true) {
                     const int kb = todo ? __builtin_ctzll(todo) : -1;  // wave-uniform
                     if (kb >= 0) {
                         todo &= todo - 1;
-                        b0 = srec[3 * kb + 0];
-                        b1 = srec[3 * kb + 1];
-                        b2 = srec[3 * kb + 2];
+                        rb = staged(srec, kb);
                         if constexpr (AUX) zb = svz[kb];
                     }
-                    if (record(ka, a0, a1, a2, za) || kb < 0) break;
+                    if (record(ka, ra, za) || kb < 0) break;
                     ka = todo ? __builtin_ctzll(todo) : -1;
                     if (ka >= 0) {
                         todo &= todo - 1;
-                        a0 = srec[3 * ka + 0];
-                        a1 = srec[3 * ka + 1];
-                        a2 = srec[3 * ka + 2];
+                        ra = staged(srec, ka);
                         if constexpr (AUX) za = svz[ka];
                     }
-                    if (record(kb, b0, b1, b2, zb) || ka < 0) break;
+                    if (record(kb, rb, zb) || ka < 0) break;
                 }
             }
         } else {
@@ -880,10 +972,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PF ? 4 : (si
                 todo &= todo - 1;
                 float vz = 0.0f;
                 if constexpr (AUX) vz = svz[k];
-                if (record(k, srec[3 * k + 0], srec[3 * k + 1], srec[3 * k + 2], vz)) break;
+                if (record(k, staged(srec, k), vz)) break;
             }
         }
-        if (parked) park_flush<AUX>(qpark, sjl, kpack, parked, p8f, p1, fl, lane, ax.pz);
+        if (parked) park_flush(flane, srec, kpack, parked, fl);
         __syncthreads();  // srec / qpark are rewritten by the next batch
     }
 }
