@@ -40,6 +40,8 @@ HIP_SOURCES = {
     "gsr_blend.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
     # recomputes the forward's SH clamp bits: must round exactly like gsr_preprocess.hip
     "gsr_preprocess_bwd.hip": ["-ffp-contract=off"],
+    # camera gradients: reads the stored clamp bits (recomputes none), tolerance-compared, default flags
+    "gsr_camera_bwd.hip": [],
     # training-step kernels (loss, fused Adam, densification): tolerance-compared, default flags
     "gsr_train.hip": [],
     # point-cloud initialisation (exact k-NN): box and point distances must round alike

@@ -896,11 +896,21 @@ int gsr_backward_views(int32_t V, const gsr_camera* cams, const gsr_gaussians* g
     return 0;
 }
 
-// gsr_backward / gsr_backward_aux (aux != nullptr, on a full image: checked by the caller), after validate()
+// the 36 camera-gradient floats of a call without Gaussians (the finalize over no partials)
+static int camera_zeros(float* dL_dcamera, hipStream_t stream) {
+    const bool debug = false;
+    GSR_CHECK_HIP(launch_camera_backward(gsr_camera{}, GaussIn{}, nullptr, nullptr, nullptr, 0, false, nullptr,
+                                         dL_dcamera, stream),
+                  "camera backward (no Gaussians)");
+    return 0;
+}
+
+// gsr_backward / gsr_backward_aux (aux != nullptr, on a full image: checked by the caller), after validate();
+// dL_dcamera != nullptr (gsr_backward_posed, full image): the camera pass follows B2
 static int backward_one(const gsr_camera* cam, const gsr_gaussians* gs, const gsr_raster_settings* rs,
                         const gsr_buffers* bufs, const float* dL_dpix, gsr_alloc_fn alloc_scratch, void* ctx,
-                        const gsr_grads* grads, void* stream_, const gsr_aux_grads* aux) {
-    if (gs->P == 0) return 0;
+                        const gsr_grads* grads, void* stream_, const gsr_aux_grads* aux, float* dL_dcamera = nullptr) {
+    if (gs->P == 0) return dL_dcamera ? camera_zeros(dL_dcamera, (hipStream_t)stream_) : 0;
     if (int e = check_grads(gs, grads)) return e;
     if (!bufs || bufs->n_local != gs->P) return fail(-1, "forward buffers do not match the Gaussians");
     {
@@ -928,6 +938,15 @@ static int backward_one(const gsr_camera* cam, const gsr_gaussians* gs, const gs
                                                                    grad_out(grads), stream, aux ? (inv ? 2 : 1) : 0,
                                                                    (rs->flags & GSR_FLAG_ANTIALIAS) != 0),
               aux ? "preprocess backward (aux)" : "preprocess backward");
+    if (dL_dcamera) {  // gsr_backward_posed: the camera pass on the same grad2d (full image: checked by the caller)
+        float* part = static_cast<float*>(alloc_scratch(ctx, camera_grad_scratch_bytes(gs->P)));
+        if (!part) return fail(-2, "allocation failed (camera gradient partials, P=%d)", gs->P);
+        GSR_STAGE(GSR_STAGE_PREPROCESS_BWD, launch_camera_backward(*cam, gauss_in(gs), v.depth_key, v.flags, grad2d,
+                                                                   aux ? (inv ? 2 : 1) : 0,
+                                                                   (rs->flags & GSR_FLAG_ANTIALIAS) != 0, part,
+                                                                   dL_dcamera, stream),
+                  "camera backward");
+    }
     return 0;
 }
 
@@ -949,6 +968,61 @@ int gsr_backward_aux(const gsr_camera* cam, const gsr_gaussians* gs, const gsr_r
         return fail(-1, "aux: full images only (tile rows [%d, %d) of %d are a band)", rs->tile_y0, rs->tile_y1,
                     div_up(cam->height, kTile));
     return backward_one(cam, gs, rs, bufs, dL_dpix, alloc_scratch, ctx, grads, stream_, aux);
+}
+
+// ---- camera gradients ----
+size_t gsr_camera_grad_scratch_bytes(int32_t P) { return camera_grad_scratch_bytes(P); }
+
+// what both camera-gradient calls refuse before anything else (after validate())
+static int check_camera_call(const char* who, const gsr_camera* cam, const gsr_raster_settings* rs,
+                             const float* dL_dcamera) {
+    if (!dL_dcamera) return fail(-1, "%s: null dL_dcamera", who);
+    if (!aligned16(dL_dcamera)) return fail(-1, "%s: dL_dcamera must be 16-byte aligned", who);
+    if (!full_image(cam, rs))
+        return fail(-1, "%s: full images only (tile rows [%d, %d) of %d are a band)", who, rs->tile_y0, rs->tile_y1,
+                    div_up(cam->height, kTile));
+    return 0;
+}
+
+int gsr_backward_camera(const gsr_camera* cam, const gsr_gaussians* gs, const gsr_raster_settings* rs,
+                        const gsr_buffers* bufs, const float* grad2d, int32_t depth_mode, void* scratch,
+                        float* dL_dcamera, void* stream_) {
+    g_err.clear();
+    if (int e = validate(cam, gs, rs)) return e;
+    if (int e = check_camera_call("gsr_backward_camera", cam, rs, dL_dcamera)) return e;
+    if (depth_mode < 0 || depth_mode > 2)
+        return fail(-1, "gsr_backward_camera: depth_mode %d is not 0 (colour), 1 (dL/dz) or 2 (dL/d(1/z))", depth_mode);
+    if (!bufs || (gs->P > 0 && !grad2d) || !scratch)
+        return fail(-1, "gsr_backward_camera: null buffers / grad2d / scratch");
+    if (!aligned16(scratch) || !aligned16(grad2d))
+        return fail(-1, "gsr_backward_camera: scratch and grad2d must be 16-byte aligned");
+    hipStream_t stream = (hipStream_t)stream_;
+    if (gs->P == 0) return camera_zeros(dL_dcamera, stream);
+    if (!bufs->geom || bufs->n_local != gs->P)
+        return fail(-1, "gsr_backward_camera: forward buffers do not match the Gaussians");
+    if (int e = check_layout(cam, 0, div_up(cam->height, kTile), bufs, rs)) return e;
+    const bool debug = (rs->flags & GSR_FLAG_DEBUG) != 0;
+    const GeomLayout gl(gs->P);
+    GSR_STAGE(GSR_STAGE_PREPROCESS_BWD,
+              launch_camera_backward(*cam, gauss_in(gs), at<uint32_t>(bufs->geom, gl.depth_key),
+                                     at<uint32_t>(bufs->geom, gl.flags), grad2d, depth_mode,
+                                     (rs->flags & GSR_FLAG_ANTIALIAS) != 0, static_cast<float*>(scratch), dL_dcamera,
+                                     stream),
+              "camera backward");
+    return 0;
+}
+
+int gsr_backward_posed(const gsr_camera* cam, const gsr_gaussians* gs, const gsr_raster_settings* rs,
+                       const gsr_buffers* bufs, const float* dL_dpix, const gsr_aux_grads* aux,
+                       gsr_alloc_fn alloc_scratch, void* ctx, const gsr_grads* grads, float* dL_dcamera,
+                       void* stream_) {
+    g_err.clear();
+    if (int e = validate(cam, gs, rs)) return e;
+    if (int e = check_camera_call("gsr_backward_posed", cam, rs, dL_dcamera)) return e;
+    if (!alloc_scratch) return fail(-1, "gsr_backward_posed: null scratch allocator");
+    if (!dL_dpix || !bufs || (gs->P > 0 && (!bufs->geom || !bufs->binning || !bufs->image)))
+        return fail(-1, "gsr_backward_posed: null forward buffers / dL_dout_color");
+    return backward_one(cam, gs, rs, bufs, dL_dpix, alloc_scratch, ctx, grads, stream_, aux, dL_dcamera);
 }
 
 int gsr_backward_blend(const gsr_camera* cam, const gsr_gaussians* gs, const gsr_raster_settings* rs,

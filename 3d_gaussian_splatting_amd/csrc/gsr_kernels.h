@@ -199,6 +199,15 @@ int launch_preprocess_backward_views(const gsr_camera* cams, int V, const GaussI
                                      const GradOut& scratch, hipStream_t s, bool aa = false);
 int launch_views_sum(const GaussIn& in, int V, const GradOut& out, const GradOut& scratch, hipStream_t s);
 
+// ---- gsr_camera_bwd.hip ----
+// The camera gradient from grad2d (one full-image view): 36 floats into dcam -- dL/dviewmatrix[16],
+// dL/dprojmatrix[16], dL/dcampos[3], 0 -- written, not accumulated; zeros for P <= 0.  flags: the
+// forward's stored SH clamp bits.  depth_mode as launch_preprocess_backward's aux.  part:
+// camera_grad_scratch_bytes(P) of block partials.  Two launches, no atomics, bitwise reproducible.
+size_t camera_grad_scratch_bytes(long long P);
+int launch_camera_backward(const gsr_camera& cam, const GaussIn& in, const uint32_t* depth_key, const uint32_t* flags,
+                           const float* grad2d, int depth_mode, bool aa, float* part, float* dcam, hipStream_t s);
+
 // ---- multi-GPU exchange (gsr_shard.hip) ----
 // Shard side: pack every visible Gaussian of [0, P) into the send block of each band its rect
 // overlaps (order-preserving; headers = true counts; slots past pair_cap dropped), remember the

@@ -52,7 +52,9 @@ EXPORTS = ["gsr_abi_version", "gsr_last_error", "gsr_forward", "gsr_read_num_ren
            "gsr_shard_state_bytes", "gsr_view", "gsr_geom_bytes", "gsr_binning_bytes",
            "gsr_image_bytes", "gsr_scratch_bytes", "gsr_ck_pool_slots", "gsr_profile_enable", "gsr_profile_read",
            "gsr_stage_name", "gsr_band_publish", "gsr_gather_finish", "gsr_forward_aux", "gsr_backward_aux",
-           "gsr_binning_bytes_aux", "gsr_image_bytes_aux", "gsr_scratch_bytes_aux"]
+           "gsr_binning_bytes_aux", "gsr_image_bytes_aux", "gsr_scratch_bytes_aux",
+           "gsr_camera_grad_scratch_bytes", "gsr_backward_camera", "gsr_backward_posed"]
+CAMERA_GRAD_FLOATS = 36  # gsr.h GSR_CAMERA_GRAD_FLOATS: dL/dviewmatrix[16], dL/dprojmatrix[16], dL/dcampos[3], 0
 # include/gsr/gsr_train.h (training-step kernels)
 TRAIN_EXPORTS = ["gsr_activate", "gsr_loss_scratch_bytes", "gsr_loss_forward", "gsr_loss_backward", "gsr_adam_step",
                  "gsr_adam_step_guarded", "gsr_adam_step_sparse", "gsr_densify_stats", "gsr_densify_stats_guarded", "gsr_compact_scratch_bytes", "gsr_compact_index", "gsr_gather_rows",
@@ -173,6 +175,16 @@ def load_hip() -> ctypes.CDLL:
         L.gsr_backward_preprocess.argtypes = [ctypes.POINTER(Camera), ctypes.POINTER(Gaussians),
                                               ctypes.POINTER(Settings), ctypes.POINTER(Buffers), vp,
                                               ctypes.POINTER(Grads), vp]
+        # camera gradients: the pass on a grad2d, and gsr_backward / gsr_backward_aux followed by it
+        L.gsr_camera_grad_scratch_bytes.restype = ctypes.c_size_t
+        L.gsr_camera_grad_scratch_bytes.argtypes = [i32]
+        L.gsr_backward_camera.restype = ctypes.c_int
+        L.gsr_backward_camera.argtypes = [ctypes.POINTER(Camera), ctypes.POINTER(Gaussians),
+                                          ctypes.POINTER(Settings), ctypes.POINTER(Buffers), vp, i32, vp, vp, vp]
+        L.gsr_backward_posed.restype = ctypes.c_int
+        L.gsr_backward_posed.argtypes = [ctypes.POINTER(Camera), ctypes.POINTER(Gaussians), ctypes.POINTER(Settings),
+                                         ctypes.POINTER(Buffers), vp, ctypes.POINTER(AuxGrads), ALLOC_FN, vp,
+                                         ctypes.POINTER(Grads), vp, vp]
         # multi-GPU split: shard F1 + pack, band F2..F6, band B1, shard sum + B2
         pi32 = ctypes.POINTER(i32)
         L.gsr_exchange_block_bytes.restype = ctypes.c_size_t

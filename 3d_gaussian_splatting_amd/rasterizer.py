@@ -271,28 +271,62 @@ class CAbiRasterizer:
                              sh_degree, colors_precomp, cov3D_precomp, scale_modifier, bg, tile_rows, max_rendered,
                              debug, antialiasing)
 
-    def _backward(self, st: ForwardState, dL_dpix, aux_grads=None) -> dict:
-        """gsr_backward, or gsr_backward_aux with aux_grads = (dL_ddepth, dL_dalpha), each None = zero."""
+    def _backward(self, st: ForwardState, dL_dpix, aux_grads=None, camera_grad=False) -> dict:
+        """gsr_backward, or gsr_backward_aux with aux_grads = (dL_ddepth, dL_dalpha), each None = zero;
+        camera_grad: gsr_backward_posed, the same call followed by the camera pass."""
         H, W = st.cam.height, st.cam.width
         dpix = _f32(dL_dpix, (3, H, W), self.device)
         out, gg = self._grad_tensors(st)
         scratch = _Allocator(self.device)
         args = (ctypes.byref(self._cam(st.cam)), ctypes.byref(st.gauss), ctypes.byref(st.settings),
                 ctypes.byref(st.buffers), _ptr(dpix), scratch.cb, None, ctypes.byref(gg), self._stream())
-        if aux_grads is None:
-            self._check(self.L.gsr_backward(*args), "gsr_backward")
-        else:
+        aux = None
+        if aux_grads is not None:
             dd, da = (_f32(t, (H, W), self.device) for t in aux_grads)
             aux = native.AuxGrads(None if dd is None else dd.data_ptr(), None if da is None else da.data_ptr())
+        if camera_grad:
+            dcam = torch.empty(native.CAMERA_GRAD_FLOATS, dtype=torch.float32, device=self.device)
+            rc = self.L.gsr_backward_posed(*args[:5], None if aux is None else ctypes.byref(aux), scratch.cb, None,
+                                           ctypes.byref(gg), _ptr(dcam), self._stream())
+            self._check(rc, "gsr_backward_posed")
+            out.update(self._camera_views(dcam))
+        elif aux is None:
+            self._check(self.L.gsr_backward(*args), "gsr_backward")
+        else:
             self._check(self.L.gsr_backward_aux(*args, ctypes.byref(aux)), "gsr_backward_aux")
         return out
 
-    def backward(self, st: ForwardState, dL_dpix) -> dict:
-        return self._backward(st, dL_dpix)
+    @staticmethod
+    def _camera_views(dcam: torch.Tensor) -> dict:
+        """The 36 floats of gsr.h's dL_dcamera ("camera") and its three fields as views of it,
+        flattened like RasterCamera's."""
+        return dict(camera=dcam, viewmatrix=dcam[0:16], projmatrix=dcam[16:32], campos=dcam[32:35])
 
-    def backward_aux(self, st: ForwardState, dL_dpix, dL_ddepth=None, dL_dalpha=None) -> dict:
-        """gsr_backward_aux: backward() for a loss over colour, depth and alpha (None = zero)."""
-        return self._backward(st, dL_dpix, (dL_ddepth, dL_dalpha))
+    def backward(self, st: ForwardState, dL_dpix, camera_grad=False) -> dict:
+        """gsr_backward.  camera_grad: gsr_backward_posed -- the same leaf gradients bit for bit, and
+        the dict gains "viewmatrix" (16,), "projmatrix" (16,), "campos" (3,): dL/d(the camera's field),
+        the three treated as independent (pose.chain ties them to a pose), device views of the
+        36-float "camera".  Full images only."""
+        return self._backward(st, dL_dpix, None, camera_grad)
+
+    def backward_aux(self, st: ForwardState, dL_dpix, dL_ddepth=None, dL_dalpha=None, camera_grad=False) -> dict:
+        """gsr_backward_aux: backward() for a loss over colour, depth and alpha (None = zero).
+        camera_grad: as backward()'s; the depth channel's dependence on the view matrix is included."""
+        return self._backward(st, dL_dpix, (dL_ddepth, dL_dalpha), camera_grad)
+
+    def backward_camera(self, st: ForwardState, grad2d: torch.Tensor, depth_mode: int = 0) -> dict:
+        """gsr_backward_camera: the camera pass alone on a (P, 12) grad2d (backward_blend's; depth_mode
+        1 / 2 read slot 9 as dL/dz / dL/d(1/z) of the depth channel).  The camera keys of backward()."""
+        grad2d = grad2d.contiguous()
+        nbytes = int(self.L.gsr_camera_grad_scratch_bytes(st.gauss.P))
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        dcam = torch.empty(native.CAMERA_GRAD_FLOATS, dtype=torch.float32, device=self.device)
+        c = self._cam(st.cam)
+        rc = self.L.gsr_backward_camera(ctypes.byref(c), ctypes.byref(st.gauss), ctypes.byref(st.settings),
+                                        ctypes.byref(st.buffers), _ptr(grad2d), int(depth_mode), _ptr(scratch),
+                                        _ptr(dcam), self._stream())
+        self._check(rc, "gsr_backward_camera")
+        return self._camera_views(dcam)
 
     def forward_batch(self, cams, means3D, opacities, scales=None, rotations=None, sh_dc=None, sh_rest=None,
                       sh_degree=0, colors_precomp=None, cov3D_precomp=None, scale_modifier=1.0,
@@ -673,4 +707,119 @@ def render(viewpoint_camera: RasterCamera, pc, pipe: PipelineParams, bg_color, s
     color, radii = rasterize_gaussians(viewpoint_camera, xyz, screenspace, pc.get_opacity, **kw)
     if exposure is not None:
         color = apply_exposure(color, exposure, clamp)
+    return dict(render=color, viewspace_points=screenspace, visibility_filter=radii > 0, radii=radii)
+
+
+# ------------------------------------------------------------------------------------------
+# pose-differentiable render (Python autograd Function over the C ABI)
+# ------------------------------------------------------------------------------------------
+_posed_rasterizers: dict = {}
+
+
+def _posed_rasterizer(device) -> CAbiRasterizer:
+    dev = torch.device(device)
+    if dev.type == "cuda" and dev.index is None:  # "cuda" and "cuda:0" are one device, one rasterizer
+        dev = torch.device("cuda", torch.cuda.current_device())
+    if dev not in _posed_rasterizers:
+        _posed_rasterizers[dev] = CAbiRasterizer(dev)
+    return _posed_rasterizers[dev]
+
+
+_POSED_TENSORS = ("means3D", "means2D", "opacities", "sh_dc", "sh_rest", "colors_precomp", "scales", "rotations",
+                  "cov3D_precomp")
+_POSED_GRAD_KEYS = dict(means3D="means3D", means2D="means2D", opacities="opacities", sh_dc="sh_dc", sh_rest="sh_rest",
+                        colors_precomp="colors", scales="scales", rotations="rotations", cov3D_precomp="cov3D")
+
+
+class _RenderPosed(torch.autograd.Function):
+    """forward / forward_aux of CAbiRasterizer on pose.compose(cam, delta); the backward is
+    gsr_backward_posed, whose 36 camera floats are read back (one small device->host copy, which waits
+    for the backward on the stream) and chained to delta in float64 on the host (pose.chain)."""
+
+    @staticmethod
+    def forward(ctx, cfg, delta, *tensors):
+        from . import pose
+        t = dict(zip(_POSED_TENSORS, tensors))
+        rast = _posed_rasterizer(t["means3D"].device)
+        cam = pose.compose(cfg["cam"], delta)
+        kw = dict(scales=t["scales"], rotations=t["rotations"], sh_dc=t["sh_dc"], sh_rest=t["sh_rest"],
+                  sh_degree=cfg["sh_degree"], colors_precomp=t["colors_precomp"], cov3D_precomp=t["cov3D_precomp"],
+                  scale_modifier=cfg["scale_modifier"], bg=cfg["bg"], debug=cfg["debug"],
+                  antialiasing=cfg["antialiasing"])
+        with torch.no_grad():
+            if cfg["inverse_depth"] is None:
+                st = rast.forward(cam, t["means3D"], t["opacities"].reshape(-1), **kw)
+            else:
+                st = rast.forward_aux(cam, t["means3D"], t["opacities"].reshape(-1),
+                                      inverse_depth=cfg["inverse_depth"], **kw)
+        ctx.rast, ctx.st, ctx.cfg, ctx.delta = rast, st, cfg, delta.detach().clone()
+        ctx.shapes = [None if x is None else tuple(x.shape) for x in tensors]
+        ctx.mark_non_differentiable(st.radii)
+        if cfg["inverse_depth"] is None:
+            return st.color, st.radii
+        return st.color, st.depth, st.alpha, st.radii
+
+    @staticmethod
+    def backward(ctx, dcolor, *rest):
+        from . import pose
+        st = ctx.st
+        if dcolor is None:
+            dcolor = torch.zeros_like(st.color)
+        if ctx.cfg["inverse_depth"] is None:
+            g = ctx.rast.backward(st, dcolor, camera_grad=True)
+        else:
+            g = ctx.rast.backward_aux(st, dcolor, rest[0], rest[1], camera_grad=True)
+        ddelta = None
+        if ctx.needs_input_grad[1]:
+            ddelta = pose.chain(ctx.cfg["cam"], ctx.delta, g["camera"].cpu())
+        grads = []
+        for i, name in enumerate(_POSED_TENSORS):
+            shape = ctx.shapes[i]
+            grads.append(None if shape is None or not ctx.needs_input_grad[2 + i]
+                         else g[_POSED_GRAD_KEYS[name]].reshape(shape))
+        return (None, ddelta, *grads)
+
+
+def render_posed(viewpoint_camera: RasterCamera, delta, pc, pipe: PipelineParams, bg_color, scaling_modifier=1.0,
+                 override_color=None, return_depth=False, inverse_depth=False) -> dict:
+    """render() of the camera pose.compose(viewpoint_camera, delta), differentiable in the Gaussians as
+    render() is and in `delta`, the (6,) float64 CPU pose correction of pose.py (requires_grad for a
+    gradient: d(loss)/d(delta) arrives on the CPU).  The dict is render()'s (with return_depth also
+    "depth" and "alpha").  A Python autograd Function over the C ABI (CAbiRasterizer), not the libtorch
+    extension: render() and the C++ gsr::render stay without pose gradients.  Each backward reads the 36
+    camera floats back to the host (one small device->host copy: it synchronises the stream).  With
+    pipe.convert_SHs_python or override_color the colours are inputs, so the view direction contributes
+    no pose gradient (gsr.h: dL/dcampos is zero with colors_precomp)."""
+    from . import pose
+    from .general import eval_sh
+    xyz = pc.get_xyz
+    delta = torch.as_tensor(delta, dtype=torch.float64)
+    if delta.device.type != "cpu" or delta.numel() != 6:
+        raise ValueError("render_posed: delta is a (6,) float64 CPU tensor")
+    screenspace = torch.zeros_like(xyz, requires_grad=True)
+    scales = rotations = cov3D = sh_dc = sh_rest = colors = None
+    if pipe.compute_cov3D_python:
+        cov3D = pc.get_covariance(scaling_modifier)
+    else:
+        scales, rotations = pc.get_scaling, pc.get_rotation
+    if override_color is not None:
+        colors = override_color
+    elif pipe.convert_SHs_python:
+        campos = torch.as_tensor(pose.compose(viewpoint_camera, delta).campos, device=xyz.device)
+        dirs = xyz - campos
+        dirs = dirs / dirs.norm(dim=1, keepdim=True)
+        colors = torch.clamp_min(eval_sh(pc.active_sh_degree, pc.get_features, dirs) + 0.5, 0.0)
+    else:
+        sh_dc, sh_rest = pc.features_dc, pc.features_rest
+    cfg = dict(cam=viewpoint_camera, sh_degree=0 if colors is not None else int(pc.active_sh_degree),
+               scale_modifier=float(scaling_modifier), bg=[float(v) for v in torch.as_tensor(bg_color).flatten().tolist()],
+               debug=bool(pipe.debug), antialiasing=bool(getattr(pipe, "antialiasing", False)),
+               inverse_depth=bool(inverse_depth) if return_depth else None)
+    out = _RenderPosed.apply(cfg, delta, xyz, screenspace, pc.get_opacity, sh_dc, sh_rest, colors, scales, rotations,
+                             cov3D)
+    if return_depth:
+        color, depth, alpha, radii = out
+        return dict(render=color, viewspace_points=screenspace, visibility_filter=radii > 0, radii=radii,
+                    depth=depth, alpha=alpha)
+    color, radii = out
     return dict(render=color, viewspace_points=screenspace, visibility_filter=radii > 0, radii=radii)

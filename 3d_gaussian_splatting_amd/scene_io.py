@@ -489,6 +489,9 @@ def save_checkpoint(path: str, state: dict) -> None:
         blob["exposure"] = {"param": cpu(ex["param"]), "exp_avg": cpu(ex["exp_avg"]), "exp_avg_sq": cpu(ex["exp_avg_sq"]),
                             "step": torch.tensor(int(ex["step"])),
                             "names": None if ex.get("names") is None else [str(n) for n in ex["names"]]}
+    ps = state.get("poses")
+    if ps is not None:  # the per-view pose corrections and their Adam state (float64, int64 step counts)
+        blob["poses"] = {k: cpu(ps[k]) for k in ("delta", "exp_avg", "exp_avg_sq", "steps")}
     torch.save(blob, path)
 
 
@@ -509,6 +512,7 @@ def load_checkpoint(path: str, device="cpu") -> dict:
     st["exposure"] = None if ex is None else {"param": ex["param"], "exp_avg": ex["exp_avg"],
                                                "exp_avg_sq": ex["exp_avg_sq"], "step": int(ex["step"].item()),
                                                "names": ex["names"]}
+    st["poses"] = raw.get("poses")  # None for a checkpoint written without poses
     return st
 
 

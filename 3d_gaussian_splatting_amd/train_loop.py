@@ -196,6 +196,9 @@ def write_scene(path: str, scene: LoopScene, iterations: int, opt: OptimizationP
     if opt.train_exposure:
         raise ValueError("write_scene: the GSRLOOP1 file has no exposure switch (the C++ loop trains without "
                          "per-view exposure); pass opt.train_exposure = False")
+    if opt.train_poses:
+        raise ValueError("write_scene: the GSRLOOP1 file has no pose switch (the C++ loop trains without pose "
+                         "refinement); pass opt.train_poses = False")
     views = view_sequence(len(scene.cams), iterations, seed) if views is None else np.asarray(views, np.int32)
     H, W = int(scene.gts[0].shape[1]), int(scene.gts[0].shape[2])
     with open(path, "wb") as f:
@@ -233,6 +236,8 @@ def train(scene: LoopScene, iterations: int | None = None, opt: OptimizationPara
                                           opt=opt, device=device, seed=seed)
     if opt.train_exposure:
         tr.setup_exposure(len(scene.cams))
+    if opt.train_poses:
+        tr.setup_poses(len(scene.cams))
     views = view_sequence(len(scene.cams), iterations, seed)
     res = LoopResult(iterations=iterations, seconds=0.0, iters_per_s=0.0)
     logged, depth_logged = [], []
@@ -240,7 +245,7 @@ def train(scene: LoopScene, iterations: int | None = None, opt: OptimizationPara
     t0 = time.perf_counter()
     for it in range(1, iterations + 1):
         v = int(views[it - 1])
-        kw = dict(view_index=v) if opt.train_exposure else {}
+        kw = dict(view_index=v) if opt.train_exposure or opt.train_poses else {}
         if scene.depths is not None:
             out = tr.step(it, scene.cams[v], scene.gts[v], gt_depth=scene.depths[v],
                           depth_mask=scene.depth_masks[v] if scene.depth_masks is not None else None, **kw)
@@ -256,6 +261,8 @@ def train(scene: LoopScene, iterations: int | None = None, opt: OptimizationPara
         if progress_every and it % progress_every == 0:
             print(f"[loop] iteration {it} points {tr.num_points} {time.perf_counter() - t0:.1f} s", file=sys.stderr,
                   flush=True)
+    if opt.train_poses:
+        tr.flush_poses()
     torch.cuda.synchronize()
     res.seconds = time.perf_counter() - t0
     res.iters_per_s = iterations / res.seconds

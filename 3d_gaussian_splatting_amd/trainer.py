@@ -46,7 +46,7 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from . import native, scene_io
+from . import native, pose, scene_io
 from .general import build_rotation, get_expon_lr_func
 from .rasterizer import CAbiRasterizer
 
@@ -105,9 +105,59 @@ class OptimizationParams:
     exposure_lr_delay_steps: int = 0
     exposure_lr_delay_mult: float = 0.0
     exposure_clamp: bool = True
+    # pose refinement (gsplat's pose_opt, the BARF family; neither upstream 3DGS nor the reference has
+    # it): one rigid correction per training view (pose.py), stepped by a host-side Adam per view row
+    # from the rasterizer's camera gradients (gsr_backward_posed), exponential LR schedule over
+    # `iterations`; the translation half's rate is multiplied by spatial_lr_scale, as the xyz rate is.
+    # Design defaults, not tuned values
+    train_poses: bool = False
+    pose_lr_init: float = 1e-4
+    pose_lr_final: float = 1e-6
+    pose_lr_delay_steps: int = 0
+    pose_lr_delay_mult: float = 0.0
 
 
 OPTIMIZER_TYPES = ("default", "sparse_adam")
+
+
+class PoseState:
+    """The per-view pose corrections and their Adam state, float64 on the host: delta (N, 6) =
+    (omega, tau) per view (pose.py), exp_avg, exp_avg_sq, and each row's own step count."""
+
+    def __init__(self, n_views: int):
+        n = int(n_views)
+        if n <= 0:
+            raise ValueError("PoseState: n_views must be positive")
+        self.delta = np.zeros((n, 6), np.float64)
+        self.exp_avg = np.zeros((n, 6), np.float64)
+        self.exp_avg_sq = np.zeros((n, 6), np.float64)
+        self.steps = np.zeros(n, np.int64)
+
+    def adam_row(self, row: int, grad, lr: float, spatial_lr_scale: float = 1.0, beta1: float = 0.9,
+                 beta2: float = 0.999, eps: float = 1e-8) -> None:
+        """One torch::optim::Adam step (default options, no weight decay) of row `row` alone, at that
+        row's step count; the translation half steps at lr * spatial_lr_scale."""
+        g = np.asarray(grad, np.float64).reshape(6)
+        self.steps[row] += 1
+        t = int(self.steps[row])
+        m, v = self.exp_avg[row], self.exp_avg_sq[row]
+        m *= beta1
+        m += (1.0 - beta1) * g
+        v *= beta2
+        v += (1.0 - beta2) * g * g
+        rates = lr * np.array([1.0, 1.0, 1.0, spatial_lr_scale, spatial_lr_scale, spatial_lr_scale])
+        denom = np.sqrt(v) / math.sqrt(1.0 - beta2 ** t) + eps
+        self.delta[row] -= (rates / (1.0 - beta1 ** t)) * (m / denom)
+
+    def state_dict(self) -> dict:
+        return {k: torch.from_numpy(getattr(self, k).copy()) for k in ("delta", "exp_avg", "exp_avg_sq", "steps")}
+
+    @classmethod
+    def from_state_dict(cls, d: dict) -> "PoseState":
+        st = cls(int(d["delta"].shape[0]))
+        for k, dt in (("delta", np.float64), ("exp_avg", np.float64), ("exp_avg_sq", np.float64), ("steps", np.int64)):
+            setattr(st, k, np.ascontiguousarray(d[k].detach().cpu().numpy(), dtype=dt).copy())
+        return st
 
 
 def _device(device) -> torch.device:
@@ -446,6 +496,9 @@ class GaussianTrainer:
         self.binning = BinningCapacity(dev)
         self.exposure = None  # (N, 3, 4) after setup_exposure
         self.exposure_names = None
+        self.poses = None  # PoseState after setup_poses
+        self._pose_pending = {}
+        self.pose_updates_dropped = 0
         self.setup(opt or OptimizationParams())
 
     @classmethod
@@ -474,7 +527,9 @@ class GaussianTrainer:
     def capture(self, path: str) -> None:
         """GaussianModel::capture (src/scene/gaussian_model.cpp:76-131, 228-246): parameters,
         statistics, SH degree, spatial LR scale and every group's Adam state, one file."""
+        self.flush_poses()
         scene_io.save_checkpoint(path, {
+            "poses": None if self.poses is None else self.poses.state_dict(),
             "active_sh_degree": self.active_sh_degree, "spatial_lr_scale": self.spatial_lr_scale,
             "cameras_extent": self.cameras_extent, "params": self.params, "max_radii2D": self.max_radii2D, "xyz_gradient_accum": self.xyz_gradient_accum,
             "denom": self.denom, "exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq, "steps": self.steps,
@@ -503,6 +558,11 @@ class GaussianTrainer:
             self.exposure = ex["param"].contiguous()
             self.exposure_exp_avg, self.exposure_exp_avg_sq = ex["exp_avg"].contiguous(), ex["exp_avg_sq"].contiguous()
             self.exposure_step, self.exposure_names = ex["step"], ex["names"]
+        ps = st.get("poses")  # absent in a checkpoint without poses: they stay unset
+        self._pose_pending = {}
+        self.poses = None if ps is None else PoseState.from_state_dict(ps)
+        if ps is not None:
+            self._pose_slots(int(self.poses.delta.shape[0]))
 
     def save_ply(self, path: str) -> None:
         """The raw leaves in the upstream point-cloud PLY layout (scene_io.save_gaussians_ply)."""
@@ -527,6 +587,15 @@ class GaussianTrainer:
         """GaussianModel::setup (gaussian_model.cpp:316-352)."""
         if opt.optimizer_type not in OPTIMIZER_TYPES:
             raise ValueError(f"optimizer_type must be one of {OPTIMIZER_TYPES}, not {opt.optimizer_type!r}")
+        for name in ("pose_lr_init", "pose_lr_final", "pose_lr_delay_mult"):
+            v = getattr(opt, name)
+            if not (math.isfinite(v) and v >= 0.0):
+                raise ValueError(f"{name} must be a finite, non-negative number, not {v!r}")
+        if (opt.pose_lr_init == 0.0) != (opt.pose_lr_final == 0.0):
+            raise ValueError("pose_lr_init and pose_lr_final must both be positive or both be 0 (frozen poses): "
+                             "the schedule interpolates their logarithms")
+        if int(opt.pose_lr_delay_steps) < 0:
+            raise ValueError(f"pose_lr_delay_steps must be >= 0, not {opt.pose_lr_delay_steps!r}")
         self.opt = opt
         self.percent_dense = opt.percent_dense
         P = self.num_points
@@ -552,6 +621,10 @@ class GaussianTrainer:
                                                     lr_delay_mult=opt.exposure_lr_delay_mult,
                                                     max_steps=opt.iterations)
         self.exposure_lr = opt.exposure_lr_init
+        self.pose_scheduler = get_expon_lr_func(opt.pose_lr_init, opt.pose_lr_final,
+                                                lr_delay_steps=opt.pose_lr_delay_steps,
+                                                lr_delay_mult=opt.pose_lr_delay_mult, max_steps=opt.iterations)
+        self.pose_lr = opt.pose_lr_init
 
     def setup_exposure(self, n_views: int, names=None):
         """Upstream's per-image exposure parameter: (N, 3, 4), every row eye(3, 4), with zero Adam
@@ -568,6 +641,53 @@ class GaussianTrainer:
         self.exposure_step = 0
         self.exposure_names = None if names is None else [str(n) for n in names]
 
+    # ---------------------------------------------------------------- pose refinement
+    def _pose_slots(self, n: int):
+        pin = torch.cuda.is_available()
+        self._pose_grad_slots = torch.zeros((n, native.CAMERA_GRAD_FLOATS), dtype=torch.float32, pin_memory=pin)
+        self._pose_k_slots = torch.zeros(n, dtype=torch.int32, pin_memory=pin)
+
+    def setup_poses(self, n_views: int):
+        """One pose correction per training view (PoseState: (N, 6) float64 deltas, all zero, with zero
+        Adam moments and step counts), kept on the host, and one pinned slot per view for the camera
+        gradient its next update is made from."""
+        self.poses = PoseState(n_views)
+        self._pose_pending = {}
+        self._pose_slots(int(n_views))
+
+    def _apply_pose(self, view: int) -> None:
+        """The update view `view`'s last step left pending, if any: wait for its copy, chain the 36
+        camera floats to the row's delta (pose.chain at the delta that was rendered) and take the
+        row's Adam step -- unless that render's K exceeded its bound (the *_guarded kernels' rule: the
+        truncated render updates nothing)."""
+        pend = self._pose_pending.pop(view, None)
+        if pend is None:
+            return
+        ev, cam, lr, bound = pend
+        ev.synchronize()
+        if bound > 0 and int(self._pose_k_slots[view]) > bound:
+            self.pose_updates_dropped += 1
+            return
+        g = pose.chain(cam, torch.from_numpy(self.poses.delta[view].copy()), self._pose_grad_slots[view].clone())
+        if not bool(torch.isfinite(g).all()):  # a non-finite gradient would poison the row for good
+            self.pose_updates_dropped += 1
+            return
+        self.poses.adam_row(view, g.numpy(), lr, self.spatial_lr_scale)
+
+    def flush_poses(self) -> None:
+        """Apply every pending pose update, in view order (waits for their copies)."""
+        for view in sorted(self._pose_pending):
+            self._apply_pose(view)
+
+    def refined_cameras(self, cams) -> list:
+        """cams[i] corrected by view i's delta (pose.compose), after flush_poses()."""
+        if self.poses is None:
+            raise ValueError("refined_cameras: setup_poses was never called")
+        if len(cams) != int(self.poses.delta.shape[0]):
+            raise ValueError("refined_cameras: one camera per pose row")
+        self.flush_poses()
+        return [pose.compose(c, self.poses.delta[i]) for i, c in enumerate(cams)]
+
     def save_exposures(self, path: str) -> None:
         """exposure.json in upstream's layout (scene_io.save_exposures); unnamed views are "0", "1", ..."""
         if self.exposure is None:
@@ -579,6 +699,7 @@ class GaussianTrainer:
         lr = self.xyz_scheduler(iteration)
         self.lr["xyz"] = lr
         self.exposure_lr = self.exposure_scheduler(iteration)
+        self.pose_lr = self.pose_scheduler(iteration)
         return lr
 
     def oneup_SH_degree(self):
@@ -629,8 +750,30 @@ class GaussianTrainer:
         step with a gradient that is zero outside that row (upstream's exposure_optimizer: the other
         rows keep moving on their decaying moments).  The dict gains "exposed" (the image the loss
         saw) and "dL_dexposure" (3, 4); "image" stays the raw render.  Without it the iteration is
-        unchanged, call for call."""
+        unchanged, call for call.
+
+        With opt.train_poses, view_index names the row of the pose corrections (setup_poses) that
+        belongs to this image, and `cam` is that view's camera as given (uncorrected): the render uses
+        pose.compose(cam, delta[view_index]), the backward is gsr_backward_posed, and its 36 camera
+        floats and the render's K go to the view's pinned slot by an asynchronous copy with an event.
+        The row's Adam step is taken from them exactly when this view is next used (waiting on the event
+        if the copy has not landed) or at flush_poses() -- never opportunistically, so step() still has
+        no host synchronisation in steady state and a run does not depend on timing.  An update whose
+        render overflowed its binning bound is dropped.  The dict gains "camera" (the corrected camera)
+        and "dL_dcamera" (36 floats, device).  Without it the iteration is unchanged, call for call."""
         opt = self.opt
+        posed = opt.train_poses
+        if posed:
+            if self.poses is None:
+                raise ValueError("step: train_poses needs setup_poses(n_views) first")
+            if view_index is None:
+                raise ValueError("step: train_poses needs the view_index of this image's pose row")
+            view_index = int(view_index)
+            if not 0 <= view_index < int(self.poses.delta.shape[0]):
+                raise ValueError(f"step: view_index {view_index} is outside the {int(self.poses.delta.shape[0])} "
+                                 "pose rows")
+            self._apply_pose(view_index)
+            base_cam, cam = cam, pose.compose(cam, self.poses.delta[view_index])
         exposed = opt.train_exposure
         if exposed:
             if self.exposure is None:
@@ -662,9 +805,18 @@ class GaussianTrainer:
             depth_stats, dd, da = self.k.depth_loss(st.depth, gt_depth, mask=depth_mask, alpha=st.alpha,
                                                     weight=depth_weight, normalized=opt.depth_normalized,
                                                     alpha_min=opt.depth_alpha_min)
-            g = self.rast.backward_aux(st, dimg, dd, da)
+            g = self.rast.backward_aux(st, dimg, dd, da, camera_grad=True) if posed else \
+                self.rast.backward_aux(st, dimg, dd, da)
         else:
-            g = self.rast.backward(st, dimg)
+            g = self.rast.backward(st, dimg, camera_grad=True) if posed else self.rast.backward(st, dimg)
+        if posed and iteration < opt.iterations:
+            bound = self._guard[1] if self._guard is not None else 0
+            self._pose_grad_slots[view_index].copy_(g["camera"], non_blocking=True)
+            if bound > 0:
+                self._pose_k_slots[view_index:view_index + 1].copy_(self._guard[0], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(self.device))
+            self._pose_pending[view_index] = (ev, base_cam, self.pose_lr, bound)
         grads = {"xyz": g["means3D"], "f_dc": g["sh_dc"], "opacity": g["opacities"], "scaling": g["scales"],
                  "rotation": g["rotations"]}
         if self.params["f_rest"].shape[1]:
@@ -696,6 +848,8 @@ class GaussianTrainer:
             out.update(depth_stats=depth_stats, depth=st.depth, alpha=st.alpha, dL_ddepth=dd)
         if exposed:
             out.update(exposed=image, dL_dexposure=dE)
+        if posed:
+            out.update(camera=cam, dL_dcamera=g["camera"])
         return out
 
     def optimizer_step(self, grads: dict, visibility: torch.Tensor | None = None):

@@ -275,6 +275,50 @@ int gsr_backward_aux(const gsr_camera* cam, const gsr_gaussians* gs, const gsr_r
                      const gsr_buffers* bufs, const float* dL_dout_color, gsr_alloc_fn alloc_scratch,
                      void* alloc_ctx, const gsr_grads* grads, void* stream, const gsr_aux_grads* aux);
 
+/* ---- Camera gradients ----
+ * The render depends on the camera through the per-Gaussian preprocess alone, which reads the three
+ * camera fields as independent inputs: viewmatrix (the view-space mean of the EWA Jacobian and of the
+ * depth channel, and the rotation rows of T = J W), projmatrix (the NDC mean) and campos (the SH view
+ * direction).  The camera pass reduces the per-Gaussian terms of their gradients over P from grad2d,
+ * the hand-off between B1 and B2: one more per-Gaussian kernel and a small finalize (one block per
+ * output entry), fixed summation order, no atomics -- two calls give the same bits.
+ *
+ * dL_dcamera: GSR_CAMERA_GRAD_FLOATS DEVICE floats, 16-B aligned, WRITTEN (not accumulated):
+ *   [0,16)  dL/dviewmatrix[i]   [16,32) dL/dprojmatrix[i]   [32,35) dL/dcampos   [35] = 0
+ * indexed like the gsr_camera fields.  Entries no kernel reads are 0: viewmatrix 4k+3,
+ * projmatrix 4k+2.  The three fields are treated as independent; the caller chains them to
+ * its pose parametrisation (e.g. projmatrix = viewmatrix x projection, campos = the centre of
+ * viewmatrix).  With P == 0, or when every Gaussian is culled, all 36 floats are zeros.
+ * The values are the derivative of the forward as it computes.  For a Gaussian whose tx / tz or
+ * ty / tz lies outside the 1.3 tan(fov / 2) guard band the forward uses cx = +-limx tz, and the camera
+ * pass differentiates that (dJ02/dtz = fx cx / tz^3), whereas dL_dmeans3D of the backward calls keeps
+ * upstream's in-band factor 2 fx cx / tz^3 there: for such Gaussians dL_dcamera and dL_dmeans3D are
+ * not each other's chain (moving the camera and moving the means the other way agree for in-band
+ * Gaussians only).
+ *
+ * The split call takes grad2d as gsr_backward_blend (or the aux backward, slot 9) left it and the
+ * forward's buffers (the depth keys and the stored SH clamp bits of the geometry buffer); depth_mode
+ * 0 ignores slot 9, 1 reads it as dL/dz of the depth channel, 2 as dL/d(1/z).  scratch: the size
+ * query's bytes of DEVICE memory, 16-B aligned.
+ * The posed call is gsr_backward, or gsr_backward_aux when aux != NULL: the same layout checks and the
+ * same leaf gradients bit for bit, then the camera pass on the same grad2d (depth mode from
+ * GSR_FLAG_INVDEPTH in the aux form); alloc_scratch is asked for one more block, last.
+ * Both: full images only (a tile band in rs is refused); a layout word without the tag, an
+ * anti-alias flag that disagrees with the layout, a null pointer or a bad depth_mode are refused
+ * (< 0, gsr_last_error) before any allocation or launch.
+ * Not covered: the views calls (gsr_forward_views / gsr_backward_views, gsr_forward_batch's views go
+ * through the per-view backward and are covered) and the multi-GPU calls (gsr_shard_*, gsr_band_*)
+ * return no camera gradients. */
+#define GSR_CAMERA_GRAD_FLOATS 36
+size_t gsr_camera_grad_scratch_bytes(int32_t P);
+int gsr_backward_camera(const gsr_camera* cam, const gsr_gaussians* gs, const gsr_raster_settings* rs,
+                        const gsr_buffers* bufs, const float* grad2d, int32_t depth_mode /*0,1,2*/,
+                        void* scratch, float* dL_dcamera, void* stream);
+int gsr_backward_posed(const gsr_camera* cam, const gsr_gaussians* gs, const gsr_raster_settings* rs,
+                       const gsr_buffers* bufs, const float* dL_dout_color, const gsr_aux_grads* aux /*nullable*/,
+                       gsr_alloc_fn alloc_scratch, void* alloc_ctx, const gsr_grads* grads, float* dL_dcamera,
+                       void* stream);
+
 /* ---- Multi-GPU: Gaussian shards x tile-row bands (the scaling version) ----
  * Rank r of N owns the Gaussian shard [g0_r, g1_r) (contiguous, in rank order) and the band
  * of tile rows [band_rows[r], band_rows[r+1]).  One step:
@@ -388,7 +432,8 @@ const void* gsr_view(const gsr_camera* cam, int32_t P, const gsr_buffers* bufs, 
 #define GSR_STAGE_FINALIZE 5       /* F5 sorted gid + tile ranges */
 #define GSR_STAGE_BLEND_FWD 6      /* F6 */
 #define GSR_STAGE_BLEND_BWD 7      /* B1 */
-#define GSR_STAGE_PREPROCESS_BWD 8 /* B2 */
+#define GSR_STAGE_PREPROCESS_BWD 8 /* B2; in gsr_backward_posed / gsr_backward_camera also the camera pass
+                                      (its kernel and finalize: about as long again as B2) */
 #define GSR_STAGE_GATHER 9         /* per-Gaussian grad2d sum of the B1 partials */
 #define GSR_STAGE_MISC 10          /* memsets, background fill, num_rendered read */
 #define GSR_STAGE_EXCHANGE 11      /* multi-GPU splat pack / unpack / gradient sum */
