@@ -10,7 +10,8 @@ them plus their main.
 
 Per-file flags: gsr_preprocess.hip is compiled with -ffp-contract=off so its key-feeding
 arithmetic is bit-identical to the CPU oracle; the blend and preprocess-backward files too
-(B1 replays the forward's alpha / T bit for bit; B2 recomputes clamp bits like F1); the
+(B1 replays the forward's alpha / T bit for bit; B2 recomputes clamp bits from the text F1
+compiles, csrc/gsr_gauss_dev.h, which needs the two files' flags equal); the
 training kernels keep hipcc's default FMA contraction (compared within tolerance).
 """
 from __future__ import annotations
@@ -38,9 +39,12 @@ HIP_SOURCES = {
     "gsr_tilesort.hip": [],
     # F6 and B1 must evaluate alpha / T identically; no SLP packing (it splits DPP-fused adds)
     "gsr_blend.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
-    # recomputes the forward's SH clamp bits: must round exactly like gsr_preprocess.hip
+    # recomputes the forward's SH clamp bits (and r, coef under anti-aliasing) from the text
+    # gsr_preprocess.hip compiles, csrc/gsr_gauss_dev.h: the bits agree because the flag is the same,
+    # so these two entries must stay equal
     "gsr_preprocess_bwd.hip": ["-ffp-contract=off"],
-    # camera gradients: reads the stored clamp bits (recomputes none), tolerance-compared, default flags
+    # camera gradients: the same header under default flags -- it reads the stored clamp bits
+    # (recomputes none) and is tolerance-compared
     "gsr_camera_bwd.hip": [],
     # training-step kernels (loss, fused Adam, densification): tolerance-compared, default flags
     "gsr_train.hip": [],

@@ -7,9 +7,9 @@
 //               rotation rows of T = J W (cov2D = T Sigma T^T)
 //   projmatrix  the NDC mean (hx, hy) / (hw + 1e-7); the 4k+2 entries are never read
 //   campos      the SH view direction normalize(p - campos)
-// One thread per Gaussian restates B2's chain (gsr_preprocess_bwd.hip preprocess_backward_one, same
-// names) up to dtx/dty/dtz, dT0/dT1, the homogeneous-divide terms and the direction gradient, and
-// instead of chaining them to the mean it multiplies them with the other factor of each camera entry.
+// One thread per Gaussian walks the chain B2 walks, through the same helpers (gsr_gauss_dev.h), up to
+// dtx/dty/dtz, dT0/dT1, the homogeneous-divide terms and the direction gradient, and instead of
+// chaining them to the mean it multiplies them with the other factor of each camera entry.
 // 27 entries are live: viewmatrix 4k+r (r < 3), projmatrix 4k+{0,1,3}, campos.
 //
 // Reduction over P: registers, a wave64 butterfly, LDS across the block's four waves, one 27-float
@@ -20,17 +20,11 @@
 // Data movement is the cost (SH-rest rows: 180 of ~290 B per visible Gaussian at degree 3): the
 // block's rows are staged through LDS by consecutive lanes reading consecutive addresses, rows of
 // culled Gaussians skipped.  The SH clamp bits are the forward's stored ones (full images only).
+#include "gsr_gauss_dev.h"
 #include "gsr_kernels.h"
 
 namespace gsr {
 namespace {
-
-__constant__ float kD2[5] = {1.0925484305920792f, -1.0925484305920792f, 0.31539156525252005f,
-                             -1.0925484305920792f, 0.5462742152960396f};
-__constant__ float kD3[7] = {-0.5900435899266435f, 2.890611442640554f, -0.4570457994644658f,
-                             0.3731763325901154f, -0.4570457994644658f, 1.445305721320277f,
-                             -0.5900435899266435f};
-constexpr float kD1 = 0.4886025119029199f;
 
 constexpr int kCamSums = 27;  // acc[0..12): viewmatrix 4k+r at 3k+r; [12..24): projmatrix 4k+{0,1,3} at 12+3k+{0,1,2}; [24..27): campos
 
@@ -141,54 +135,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 3))) voi
         if (stage) {
             const float* rest = sh_lds + threadIdx.x * M3;
             const int D = in.D, nb = (D + 1) * (D + 1);
-            const float vx = p0 - cam.campos[0], vy = p1 - cam.campos[1], vz = p2 - cam.campos[2];
-            const float len = sqrtf(vx * vx + vy * vy + vz * vz);
-            const float x = vx / len, y = vy / len, z = vz / len;
-            float dbx[16], dby[16], dbz[16];
-#pragma unroll
-            for (int k = 0; k < 16; ++k) dbx[k] = dby[k] = dbz[k] = 0.f;
-            dby[1] = -kD1; dbz[2] = kD1; dbx[3] = -kD1;
-            if (D >= 2) {
-                const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
-                dbx[4] = kD2[0] * y; dby[4] = kD2[0] * x;
-                dby[5] = kD2[1] * z; dbz[5] = kD2[1] * y;
-                dbx[6] = kD2[2] * -2.f * x; dby[6] = kD2[2] * -2.f * y; dbz[6] = kD2[2] * 4.f * z;
-                dbx[7] = kD2[3] * z; dbz[7] = kD2[3] * x;
-                dbx[8] = kD2[4] * 2.f * x; dby[8] = kD2[4] * -2.f * y;
-                if (D >= 3) {
-                    dbx[9] = kD3[0] * 6.f * xy; dby[9] = kD3[0] * 3.f * (xx - yy);
-                    dbx[10] = kD3[1] * yz; dby[10] = kD3[1] * xz; dbz[10] = kD3[1] * xy;
-                    dbx[11] = kD3[2] * -2.f * xy; dby[11] = kD3[2] * (4.f * zz - xx - 3.f * yy); dbz[11] = kD3[2] * 8.f * yz;
-                    dbx[12] = kD3[3] * -6.f * xz; dby[12] = kD3[3] * -6.f * yz; dbz[12] = kD3[3] * (6.f * zz - 3.f * xx - 3.f * yy);
-                    dbx[13] = kD3[4] * (4.f * zz - 3.f * xx - yy); dby[13] = kD3[4] * -2.f * xy; dbz[13] = kD3[4] * 8.f * xz;
-                    dbx[14] = kD3[5] * 2.f * xz; dby[14] = kD3[5] * -2.f * yz; dbz[14] = kD3[5] * (xx - yy);
-                    dbx[15] = kD3[6] * 3.f * (xx - yy); dby[15] = kD3[6] * -6.f * xy;
-                }
-            }
+            const ViewDir d = view_dir(cam.campos, p0, p1, p2);
+            float basis[16], dbx[16], dby[16], dbz[16];  // the basis itself is not used here
+            sh_basis<true>(D, d.x, d.y, d.z, basis, dbx, dby, dbz);
             const float dres[3] = {(cl & 1u) ? 0.f : g2[6], (cl & 2u) ? 0.f : g2[7], (cl & 4u) ? 0.f : g2[8]};
             float ddx = 0.f, ddy = 0.f, ddz = 0.f;
+            sh_dir_grad<false>(nb, in.M_rest, dbx, dby, dbz, rest, dres, ddx, ddy, ddz);
+            float dmv[3];
+            sh_dir_to_mean(d, ddx, ddy, ddz, dmv);
 #pragma unroll
-            for (int k = 1; k < 16; ++k) {
-                if (k > in.M_rest) break;
-                if (k < nb) {
-                    const float sdot = rest[3 * (k - 1) + 0] * dres[0] + rest[3 * (k - 1) + 1] * dres[1] +
-                                       rest[3 * (k - 1) + 2] * dres[2];
-                    ddx += dbx[k] * sdot;
-                    ddy += dby[k] * sdot;
-                    ddz += dbz[k] * sdot;
-                }
-            }
-            const float dd = x * ddx + y * ddy + z * ddz;
-            acc[24] = -((ddx - x * dd) / len);
-            acc[25] = -((ddy - y * dd) / len);
-            acc[26] = -((ddz - z * dd) / len);
+            for (int k = 0; k < 3; ++k) acc[24 + k] = -dmv[k];  // the direction is p - campos
         }
         // ---- projmatrix, through the NDC mean ----
         {
-            const float hx = Pm[0] * p0 + Pm[4] * p1 + Pm[8] * p2 + Pm[12];
-            const float hy = Pm[1] * p0 + Pm[5] * p1 + Pm[9] * p2 + Pm[13];
-            const float hw = Pm[3] * p0 + Pm[7] * p1 + Pm[11] * p2 + Pm[15];
-            const float mw = 1.0f / (hw + 0.0000001f);
+            const ClipMean h = clip_mean(Pm, p0, p1, p2);
+            const float hx = h.hx, hy = h.hy, mw = h.mw;
             const float dhx = mw * g2[0], dhy = mw * g2[1];
             const float dhw = -(hx * g2[0] + hy * g2[1]) * (mw * mw);
 #pragma unroll
@@ -201,97 +162,30 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 3))) voi
         }
         // ---- viewmatrix: conic -> cov2D -> T = J W and the view-space mean ----
         if (!in.cov3D) {
-            const float r = c3[0], x = c3[1], y = c3[2], z = c3[3];
-            float R[9];
-            R[0] = 1.f - 2.f * (y * y + z * z);
-            R[1] = 2.f * (x * y - r * z);
-            R[2] = 2.f * (x * z + r * y);
-            R[3] = 2.f * (x * y + r * z);
-            R[4] = 1.f - 2.f * (x * x + z * z);
-            R[5] = 2.f * (y * z - r * x);
-            R[6] = 2.f * (x * z - r * y);
-            R[7] = 2.f * (y * z + r * x);
-            R[8] = 1.f - 2.f * (x * x + y * y);
-            const float se[3] = {in.smod * s3[0], in.smod * s3[1], in.smod * s3[2]};
-            float L[9];
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-#pragma unroll
-                for (int j = 0; j < 3; ++j) L[3 * i + j] = R[3 * i + j] * se[j];
-            c3[0] = L[0] * L[0] + L[1] * L[1] + L[2] * L[2];
-            c3[1] = L[0] * L[3] + L[1] * L[4] + L[2] * L[5];
-            c3[2] = L[0] * L[6] + L[1] * L[7] + L[2] * L[8];
-            c3[3] = L[3] * L[3] + L[4] * L[4] + L[5] * L[5];
-            c3[4] = L[3] * L[6] + L[4] * L[7] + L[5] * L[8];
-            c3[5] = L[6] * L[6] + L[7] * L[7] + L[8] * L[8];
+            float R[9], se[3];
+            cov3d_from_scale_rot(make_float4(c3[0], c3[1], c3[2], c3[3]), s3[0], s3[1], s3[2], in.smod, R, se, c3);
         }
-        const float tx = V[0] * p0 + V[4] * p1 + V[8] * p2 + V[12];
-        const float ty = V[1] * p0 + V[5] * p1 + V[9] * p2 + V[13];
-        const float tz = V[2] * p0 + V[6] * p1 + V[10] * p2 + V[14];
-        const float Wf = (float)cam.width, Hf = (float)cam.height;
-        const float fx = Wf / (2.0f * cam.tanfovx), fy = Hf / (2.0f * cam.tanfovy);
-        const float limx = 1.3f * cam.tanfovx, limy = 1.3f * cam.tanfovy;
-        const float txtz = tx / tz, tytz = ty / tz;
-        const float cx = fminf(limx, fmaxf(-limx, txtz)) * tz;
-        const float cy = fminf(limy, fmaxf(-limy, tytz)) * tz;
-        const float xmul = (txtz < -limx || txtz > limx) ? 0.f : 1.f;
-        const float ymul = (tytz < -limy || tytz > limy) ? 0.f : 1.f;
-        const float tz2 = tz * tz, tz3 = tz2 * tz;
-        const float J00 = fx / tz, J02 = -(fx * cx) / tz2, J11 = fy / tz, J12 = -(fy * cy) / tz2;
-        float T0[3], T1[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            T0[k] = J00 * V[4 * k + 0] + J02 * V[4 * k + 2];
-            T1[k] = J11 * V[4 * k + 1] + J12 * V[4 * k + 2];
-        }
-        const float S[9] = {c3[0], c3[1], c3[2], c3[1], c3[3], c3[4], c3[2], c3[4], c3[5]};
-        float ST0[3], ST1[3];
+        float t[3];
+        view_mean(V, p0, p1, p2, t);
+        const Ewa E = ewa_project(cam, t, c3);
+        Cov2dGrad G = cov2d_grad(E, g2[2], g2[3], g2[4]);
+        if (aa) aa_cov2d_grad(E, opac_in, g2[5], G);  // the chain through coef
+        const TJGrad dj = tj_grad(E, V, G);
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
-            ST0[i] = S[3 * i + 0] * T0[0] + S[3 * i + 1] * T0[1] + S[3 * i + 2] * T0[2];
-            ST1[i] = S[3 * i + 0] * T1[0] + S[3 * i + 1] * T1[1] + S[3 * i + 2] * T1[2];
-        }
-        const float a0 = ST0[0] * T0[0] + ST0[1] * T0[1] + ST0[2] * T0[2];  // cov2D before the dilation
-        const float a = a0 + 0.3f;
-        const float b = ST0[0] * T1[0] + ST0[1] * T1[1] + ST0[2] * T1[2];
-        const float c0 = ST1[0] * T1[0] + ST1[1] * T1[1] + ST1[2] * T1[2];
-        const float c = c0 + 0.3f;
-        const float det = a * c - b * b;
-        const float dA = g2[2], dB = g2[3], dC = g2[4];
-        const float inv2 = 1.0f / (det * det);
-        float dL_da = inv2 * (-c * c * dA + b * c * dB - b * b * dC);
-        float dL_db = inv2 * (2.f * b * c * dA - (a * c + b * b) * dB + 2.f * a * b * dC);
-        float dL_dc = inv2 * (-b * b * dA + a * b * dB - a * a * dC);
-        if (aa) {  // the chain through coef = sqrt(max(0.000025, det0 / det)), as in B2
-            const float h = 0.3f;
-            const float r = (a0 * c0 - b * b) / det;
-            const float coef = sqrtf(fmaxf(0.000025f, r));
-            const float dL_dr = r <= 0.000025f ? 0.f : (opac_in * g2[5]) / (2.f * coef);
-            dL_da += dL_dr * ((h * (c0 * c0 + b * b) + h * h * c0) * inv2);
-            dL_dc += dL_dr * ((h * (a0 * a0 + b * b) + h * h * a0) * inv2);
-            dL_db += dL_dr * (-2.f * b * (h * (a0 + c0) + h * h) * inv2);
-        }
-        float dJ00 = 0.f, dJ02 = 0.f, dJ11 = 0.f, dJ12 = 0.f;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const float dT0 = 2.f * ST0[i] * dL_da + ST1[i] * dL_db;
-            const float dT1 = 2.f * ST1[i] * dL_dc + ST0[i] * dL_db;
-            dJ00 += dT0 * V[4 * i + 0];
-            dJ02 += dT0 * V[4 * i + 2];
-            dJ11 += dT1 * V[4 * i + 1];
-            dJ12 += dT1 * V[4 * i + 2];
             // T0_i = J00 V[4i] + J02 V[4i+2], T1_i = J11 V[4i+1] + J12 V[4i+2]
-            acc[3 * i + 0] = dT0 * J00;
-            acc[3 * i + 1] = dT1 * J11;
-            acc[3 * i + 2] = dT0 * J02 + dT1 * J12;
+            acc[3 * i + 0] = dj.dT0[i] * E.J00;
+            acc[3 * i + 1] = dj.dT1[i] * E.J11;
+            acc[3 * i + 2] = dj.dT0[i] * E.J02 + dj.dT1[i] * E.J12;
         }
+        const float tz2 = E.tz2, tz3 = tz2 * E.tz, fx = E.fx, fy = E.fy;
         // Outside the guard band cx = +-limx tz, so J02 = -+fx limx / tz and dJ02/dtz = fx cx / tz^3: half
         // the in-band 2 fx cx / tz^3.  B2 keeps upstream's in-band factor for both (it treats a clamped cx
         // as a constant); here the forward's own derivative is taken, which is what float64 autograd of
         // the forward gives.
-        const float dt[3] = {xmul * (-fx / tz2) * dJ02, ymul * (-fy / tz2) * dJ12,
-                             (-fx / tz2) * dJ00 + (-fy / tz2) * dJ11 + ((1.f + xmul) * fx * cx / tz3) * dJ02 +
-                                 ((1.f + ymul) * fy * cy / tz3) * dJ12 +
+        const float dt[3] = {E.xmul * (-fx / tz2) * dj.dJ02, E.ymul * (-fy / tz2) * dj.dJ12,
+                             (-fx / tz2) * dj.dJ00 + (-fy / tz2) * dj.dJ11 + ((1.f + E.xmul) * fx * E.cx / tz3) * dj.dJ02 +
+                                 ((1.f + E.ymul) * fy * E.cy / tz3) * dj.dJ12 +
                                  (depth_mode == 1 ? gz : depth_mode == 2 ? -gz / tz2 : 0.f)};
 #pragma unroll
         for (int r = 0; r < 3; ++r) {

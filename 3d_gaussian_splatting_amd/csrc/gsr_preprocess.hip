@@ -7,27 +7,23 @@
 // the sort order are bit-exact.  sqrtf / division are correctly rounded under
 // hipcc's defaults (no fast-math).
 //
-// Reference anchors: quaternion layout (w,x,y,z) src/utils/general_utils.cpp:24-37;
-// L = R diag(s) :91-97; Sigma = L L^T src/scene/gaussian_model.cpp:23-24; activated inputs
-// gaussian_model.cpp:270-298; camera matrices src/scene/camera.cpp:66-71.
+// The projection chain itself (covariance, means, EWA, anti-aliasing coefficient, SH basis and
+// colour sum) is gsr_gauss_dev.h's, shared with B2 and the camera pass; this file keeps the loads,
+// the SH staging, radius / rect / tiles and the blend record.
+//
+// Reference anchors: activated inputs src/scene/gaussian_model.cpp:270-298; camera matrices
+// src/scene/camera.cpp:66-71.
 //
 // Roofline: HBM-bound.  Algorithmic bytes per Gaussian: 44 B params + 12*M B SH (visible
 // only) in; radius, depth key, tiles (12 B) + 48 B record + 16 B rect out.
 // For a band (multi-GPU) only the band's candidates evaluate SH and write records.
 #include <cstdlib>
 
+#include "gsr_gauss_dev.h"
 #include "gsr_kernels.h"
 
 namespace gsr {
 namespace {
-
-__constant__ float kSH_C2[5] = {1.0925484305920792f, -1.0925484305920792f, 0.31539156525252005f,
-                                -1.0925484305920792f, 0.5462742152960396f};
-__constant__ float kSH_C3[7] = {-0.5900435899266435f, 2.890611442640554f, -0.4570457994644658f,
-                                0.3731763325901154f, -0.4570457994644658f, 1.445305721320277f,
-                                -0.5900435899266435f};
-constexpr float kSH_C0 = 0.28209479177387814f;
-constexpr float kSH_C1 = 0.4886025119029199f;
 
 __device__ inline int imin(int a, int b) { return a < b ? a : b; }
 __device__ inline int imax(int a, int b) { return a > b ? a : b; }
@@ -81,21 +77,16 @@ __device__ __forceinline__ Params load_params(const GaussIn& in, int g) {
 template <bool AA>
 __device__ __forceinline__ Geo preprocess_geom(const gsr_camera& cam, const GaussIn& in, const Params& I, int grid_x,
                                                int grid_y, int ty0, int ty1) {
-    const float* V = cam.viewmatrix;
-    const float* Pm = cam.projmatrix;
     const float p0 = I.p0, p1 = I.p1, p2 = I.p2;
     Geo G{};
     G.key = 0xFFFFFFFFu;
 
-    const float tx = V[0] * p0 + V[4] * p1 + V[8] * p2 + V[12];
-    const float ty = V[1] * p0 + V[5] * p1 + V[9] * p2 + V[13];
-    const float tz = V[2] * p0 + V[6] * p1 + V[10] * p2 + V[14];
+    float t[3];
+    view_mean(cam.viewmatrix, p0, p1, p2, t);
+    const float tz = t[2];
     if (tz > 0.2f) {
-        const float hx = Pm[0] * p0 + Pm[4] * p1 + Pm[8] * p2 + Pm[12];
-        const float hy = Pm[1] * p0 + Pm[5] * p1 + Pm[9] * p2 + Pm[13];
-        const float hw = Pm[3] * p0 + Pm[7] * p1 + Pm[11] * p2 + Pm[15];
-        const float pw = 1.0f / (hw + 0.0000001f);
-        const float px = hx * pw, py = hy * pw;
+        const ClipMean h = clip_mean(cam.projmatrix, p0, p1, p2);
+        const float px = h.hx * h.mw, py = h.hy * h.mw;
         float c3[6];
         if (in.cov3D) {
             c3[0] = I.q.x;
@@ -105,66 +96,14 @@ __device__ __forceinline__ Geo preprocess_geom(const gsr_camera& cam, const Gaus
             c3[4] = I.s0;
             c3[5] = I.s1;
         } else {
-            const float r = I.q.x, x = I.q.y, y = I.q.z, z = I.q.w;
-            float R[9];
-            R[0] = 1.f - 2.f * (y * y + z * z);
-            R[1] = 2.f * (x * y - r * z);
-            R[2] = 2.f * (x * z + r * y);
-            R[3] = 2.f * (x * y + r * z);
-            R[4] = 1.f - 2.f * (x * x + z * z);
-            R[5] = 2.f * (y * z - r * x);
-            R[6] = 2.f * (x * z - r * y);
-            R[7] = 2.f * (y * z + r * x);
-            R[8] = 1.f - 2.f * (x * x + y * y);
-            const float sx = in.smod * I.s0;
-            const float sy = in.smod * I.s1;
-            const float sz = in.smod * I.s2;
-            float L[9];
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                L[3 * i + 0] = R[3 * i + 0] * sx;
-                L[3 * i + 1] = R[3 * i + 1] * sy;
-                L[3 * i + 2] = R[3 * i + 2] * sz;
-            }
-#define SIG(i, j) (L[3 * (i) + 0] * L[3 * (j) + 0] + L[3 * (i) + 1] * L[3 * (j) + 1] + L[3 * (i) + 2] * L[3 * (j) + 2])
-            c3[0] = SIG(0, 0);
-            c3[1] = SIG(0, 1);
-            c3[2] = SIG(0, 2);
-            c3[3] = SIG(1, 1);
-            c3[4] = SIG(1, 2);
-            c3[5] = SIG(2, 2);
-#undef SIG
+            float R[9], se[3];
+            cov3d_from_scale_rot(I.q, I.s0, I.s1, I.s2, in.smod, R, se, c3);
         }
+        const Ewa E = ewa_project(cam, t, c3);
         const float Wf = (float)cam.width, Hf = (float)cam.height;
-        const float fx = Wf / (2.0f * cam.tanfovx);
-        const float fy = Hf / (2.0f * cam.tanfovy);
-        const float limx = 1.3f * cam.tanfovx, limy = 1.3f * cam.tanfovy;
-        const float txtz = tx / tz, tytz = ty / tz;
-        const float cx = fminf(limx, fmaxf(-limx, txtz)) * tz;
-        const float cy = fminf(limy, fmaxf(-limy, tytz)) * tz;
-        const float tz2 = tz * tz;
-        const float J00 = fx / tz, J02 = -(fx * cx) / tz2;
-        const float J11 = fy / tz, J12 = -(fy * cy) / tz2;
-        float T0[3], T1[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            T0[k] = J00 * V[4 * k + 0] + J02 * V[4 * k + 2];
-            T1[k] = J11 * V[4 * k + 1] + J12 * V[4 * k + 2];
-        }
-        const float S[9] = {c3[0], c3[1], c3[2], c3[1], c3[3], c3[4], c3[2], c3[4], c3[5]};
-        float U0[3], U1[3];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            U0[j] = T0[0] * S[0 + j] + T0[1] * S[3 + j] + T0[2] * S[6 + j];
-            U1[j] = T1[0] * S[0 + j] + T1[1] * S[3 + j] + T1[2] * S[6 + j];
-        }
-        const float a0 = U0[0] * T0[0] + U0[1] * T0[1] + U0[2] * T0[2];
-        const float b = U0[0] * T1[0] + U0[1] * T1[1] + U0[2] * T1[2];
-        const float c0 = U1[0] * T1[0] + U1[1] * T1[1] + U1[2] * T1[2];
-        const float a = a0 + 0.3f, c = c0 + 0.3f;
-        const float det = a * c - b * b;
+        const float a = E.a, b = E.b, c = E.c, det = E.det;
         if (det != 0.0f) {
-            if (AA) G.coef = sqrtf(fmaxf(0.000025f, (a0 * c0 - b * b) / det));
+            if (AA) G.coef = aa_coef(aa_ratio(E));
             const float det_inv = 1.0f / det;
             const float cA = c * det_inv, cB = -b * det_inv, cC = a * det_inv;
             const float mid = 0.5f * (a + c);
@@ -200,40 +139,6 @@ __device__ __forceinline__ Geo preprocess_geom(const gsr_camera& cam, const Gaus
         }
     }
     return G;
-}
-
-// Real SH basis (degree <= 3) of the unit view direction of Gaussian g.
-__device__ __forceinline__ void sh_basis(const gsr_camera& cam, const GaussIn& in, const Params& I,
-                                         float (&basis)[16]) {
-    const float dx = I.p0 - cam.campos[0], dy = I.p1 - cam.campos[1], dz = I.p2 - cam.campos[2];
-    const float len = sqrtf(dx * dx + dy * dy + dz * dz);
-    const float x = dx / len, y = dy / len, z = dz / len;
-    const int D = in.D;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) basis[k] = 0.0f;
-    basis[0] = kSH_C0;
-    if (D >= 1) {
-        basis[1] = -kSH_C1 * y;
-        basis[2] = kSH_C1 * z;
-        basis[3] = -kSH_C1 * x;
-    }
-    if (D >= 2) {
-        const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
-        basis[4] = kSH_C2[0] * xy;
-        basis[5] = kSH_C2[1] * yz;
-        basis[6] = kSH_C2[2] * (2.0f * zz - xx - yy);
-        basis[7] = kSH_C2[3] * xz;
-        basis[8] = kSH_C2[4] * (xx - yy);
-        if (D >= 3) {
-            basis[9] = kSH_C3[0] * y * (3.0f * xx - yy);
-            basis[10] = kSH_C3[1] * xy * z;
-            basis[11] = kSH_C3[2] * y * (4.0f * zz - xx - yy);
-            basis[12] = kSH_C3[3] * z * (2.0f * zz - 3.0f * xx - 3.0f * yy);
-            basis[13] = kSH_C3[4] * x * (4.0f * zz - xx - yy);
-            basis[14] = kSH_C3[5] * z * (xx - yy);
-            basis[15] = kSH_C3[6] * x * (xx - 3.0f * yy);
-        }
-    }
 }
 
 // Blend record (SURVEY B.3 power with -0.5 and log2(e) folded in, so the blend evaluates exp2
@@ -352,7 +257,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void p
         rgb[1] = I.c1;
         rgb[2] = I.c2;
         if (!in.colors) {
-            sh_basis(cam, in, I, basis);
+            const ViewDir d = view_dir(cam.campos, I.p0, I.p1, I.p2);
+            sh_basis<false>(in.D, d.x, d.y, d.z, basis);
 #pragma unroll
             for (int ch = 0; ch < 3; ++ch) rgb[ch] = basis[0] * rgb[ch];
         }
@@ -361,15 +267,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void p
         if (SH == kShGlds) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's DMAs have landed
             if (need) {
-                const float* rest = sh_lds + wv * gq * 256 + ln * M3;
-#pragma unroll
-                for (int ch = 0; ch < 3; ++ch) {
-                    float r = rgb[ch];
-#pragma unroll
-                    for (int k = 1; k < 16; ++k)
-                        if (k < nb) r = r + basis[k] * rest[3 * (k - 1) + ch];
-                    rgb[ch] = r;
-                }
+                sh_accum<15>(rgb, basis, 1, nb, sh_lds + wv * gq * 256 + ln * M3);
             }
         } else if (SH == kShChunks) {
 #pragma unroll
@@ -382,38 +280,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void p
                     for (int j = 0; j < 16; ++j) sh_lds[(r0 + 16 * j) * kChunkF + col] = pre[j];
                 if (c < 2 && k0 + kChunkK < nb) load_chunk(c + 1);
                 __syncthreads();
-                if (need) {
-                    const float* rest = sh_lds + threadIdx.x * kChunkF;
-#pragma unroll
-                    for (int kk = 0; kk < kChunkK; ++kk) {
-                        const int k = k0 + kk;
-                        if (k < nb)
-#pragma unroll
-                            for (int ch = 0; ch < 3; ++ch) rgb[ch] = rgb[ch] + basis[k] * rest[3 * kk + ch];
-                    }
-                }
+                if (need) sh_accum<kChunkK>(rgb, basis, k0, nb, sh_lds + threadIdx.x * kChunkF);
             }
         } else if (need) {
-            const float* rest = in.sh_rest + (size_t)g * M3;
-#pragma unroll
-            for (int ch = 0; ch < 3; ++ch) {
-                float r = rgb[ch];
-#pragma unroll
-                for (int k = 1; k < 16; ++k)
-                    if (k < nb) r = r + basis[k] * rest[3 * (k - 1) + ch];
-                rgb[ch] = r;
-            }
+            sh_accum<15>(rgb, basis, 1, nb, in.sh_rest + (size_t)g * M3);
         }
     }
     if (need) {
         uint32_t clamped = 0;
         if (!in.colors) {
 #pragma unroll
-            for (int ch = 0; ch < 3; ++ch) {
-                const float r = rgb[ch] + 0.5f;
-                clamped |= (r < 0.0f ? 1u : 0u) << ch;
-                rgb[ch] = fmaxf(r, 0.0f);
-            }
+            for (int ch = 0; ch < 3; ++ch) clamped |= (sh_clamp(rgb[ch]) ? 1u : 0u) << ch;
         }
         write_record(e, I.opac, G, rgb, clamped, out);
     }

@@ -7,25 +7,18 @@
 // emission order (rect row-major), read from the contiguous range [inst_start[g], +tiles[g])
 // by gather_grad2d_kernel -- a fixed order, so results are bitwise reproducible run to run.
 //
-// Derivation (restated; same formulas as oracle/gsr_oracle.c
-// preprocess_backward_one): conic (A,B,C) = inv([[a,b],[b,c]]), cov2D = T Sigma T^T with
-// T = J W, J the EWA Jacobian (x/y terms zeroed outside the 1.3 tan(fov) clamp), Sigma = L L^T,
-// L = R(q) diag(mod s) (src/utils/general_utils.cpp:24-37,91-97), SH basis derivatives w.r.t.
-// the normalised view direction, NDC mean through the homogeneous divide.
+// Derivation: SURVEY Appendix B.5; same formulas as oracle/gsr_oracle.c preprocess_backward_one.
+// The forward values it needs and the gradients through SH, the homogeneous divide, cov2D and
+// T = J W are gsr_gauss_dev.h's (shared with F1 and the camera pass); this file keeps the loads
+// and staging, the chain from t to the mean (with upstream's guard-band factor), dSigma and the
+// scale / rotation gradients.
 //
 // Roofline: HBM-bound (V*(80+12M) + N*(60+12M) bytes).
+#include "gsr_gauss_dev.h"
 #include "gsr_kernels.h"
 
 namespace gsr {
 namespace {
-
-__constant__ float kC2[5] = {1.0925484305920792f, -1.0925484305920792f, 0.31539156525252005f,
-                             -1.0925484305920792f, 0.5462742152960396f};
-__constant__ float kC3[7] = {-0.5900435899266435f, 2.890611442640554f, -0.4570457994644658f,
-                             0.3731763325901154f, -0.4570457994644658f, 1.445305721320277f,
-                             -0.5900435899266435f};
-constexpr float kC0 = 0.28209479177387814f;
-constexpr float kC1 = 0.4886025119029199f;
 
 // Per-Gaussian sum of its per-(tile, instance) partials in emission order.  A block owns 256
 // consecutive Gaussians; their segments [offsets[g-1], offsets[g]) tile one contiguous
@@ -291,108 +284,43 @@ __device__ __forceinline__ void preprocess_backward_one(const gsr_camera& cam, c
         out.colors[3 * o + 1] = g2[7];
         out.colors[3 * o + 2] = g2[8];
     } else {
-        const float vx = p0 - cam.campos[0], vy = p1 - cam.campos[1], vz = p2 - cam.campos[2];
-        const float len = sqrtf(vx * vx + vy * vy + vz * vz);
-        const float x = vx / len, y = vy / len, z = vz / len;
+        const ViewDir d = view_dir(cam.campos, p0, p1, p2);
         float basis[16], dbx[16], dby[16], dbz[16];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) basis[k] = dbx[k] = dby[k] = dbz[k] = 0.f;
-        basis[0] = kC0;
-        if (D >= 1) {
-            basis[1] = -kC1 * y; basis[2] = kC1 * z; basis[3] = -kC1 * x;
-            dby[1] = -kC1; dbz[2] = kC1; dbx[3] = -kC1;
-        }
-        if (D >= 2) {
-            const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
-            basis[4] = kC2[0] * xy;
-            basis[5] = kC2[1] * yz;
-            basis[6] = kC2[2] * (2.0f * zz - xx - yy);
-            basis[7] = kC2[3] * xz;
-            basis[8] = kC2[4] * (xx - yy);
-            dbx[4] = kC2[0] * y; dby[4] = kC2[0] * x;
-            dby[5] = kC2[1] * z; dbz[5] = kC2[1] * y;
-            dbx[6] = kC2[2] * -2.f * x; dby[6] = kC2[2] * -2.f * y; dbz[6] = kC2[2] * 4.f * z;
-            dbx[7] = kC2[3] * z; dbz[7] = kC2[3] * x;
-            dbx[8] = kC2[4] * 2.f * x; dby[8] = kC2[4] * -2.f * y;
-            if (D >= 3) {
-                basis[9] = kC3[0] * y * (3.0f * xx - yy);
-                basis[10] = kC3[1] * xy * z;
-                basis[11] = kC3[2] * y * (4.0f * zz - xx - yy);
-                basis[12] = kC3[3] * z * (2.0f * zz - 3.0f * xx - 3.0f * yy);
-                basis[13] = kC3[4] * x * (4.0f * zz - xx - yy);
-                basis[14] = kC3[5] * z * (xx - yy);
-                basis[15] = kC3[6] * x * (xx - 3.0f * yy);
-                dbx[9] = kC3[0] * 6.f * xy; dby[9] = kC3[0] * 3.f * (xx - yy);
-                dbx[10] = kC3[1] * yz; dby[10] = kC3[1] * xz; dbz[10] = kC3[1] * xy;
-                dbx[11] = kC3[2] * -2.f * xy; dby[11] = kC3[2] * (4.f * zz - xx - 3.f * yy); dbz[11] = kC3[2] * 8.f * yz;
-                dbx[12] = kC3[3] * -6.f * xz; dby[12] = kC3[3] * -6.f * yz; dbz[12] = kC3[3] * (6.f * zz - 3.f * xx - 3.f * yy);
-                dbx[13] = kC3[4] * (4.f * zz - 3.f * xx - yy); dby[13] = kC3[4] * -2.f * xy; dbz[13] = kC3[4] * 8.f * xz;
-                dbx[14] = kC3[5] * 2.f * xz; dby[14] = kC3[5] * -2.f * yz; dbz[14] = kC3[5] * (xx - yy);
-                dbx[15] = kC3[6] * 3.f * (xx - yy); dby[15] = kC3[6] * -6.f * xy;
-            }
-        }
+        sh_basis<true>(D, d.x, d.y, d.z, basis, dbx, dby, dbz);
         // Clamp bits of the forward's SH->RGB: stored by a full-image forward, else recomputed
-        // with the forward's exact arithmetic (same basis expressions and summation order, both
-        // files built -ffp-contract=off; gsr_preprocess.hip) -- a banded forward skips SH for
-        // Gaussians outside its band, which B2 on this rank's slice may still need.
+        // by the forward's own text (view_dir, sh_basis, sh_accum, sh_clamp of gsr_gauss_dev.h,
+        // both files built -ffp-contract=off) -- a banded forward skips SH for Gaussians outside
+        // its band, which B2 on this rank's slice may still need.
         uint32_t cl = 0;
         if (flags) {
             cl = bi.cl;
         } else {
+            float rgb[3];
 #pragma unroll
-        for (int ch = 0; ch < 3; ++ch) {
-            float r = basis[0] * in.sh_dc[3 * g + ch];
-            if (lrest) {
+            for (int ch = 0; ch < 3; ++ch) rgb[ch] = basis[0] * in.sh_dc[3 * g + ch];
+            if (lrest) sh_accum<15>(rgb, basis, 1, nb, lrest);
 #pragma unroll
-                for (int k = 1; k < 16; ++k)
-                    if (k < nb) r = r + basis[k] * lrest[3 * (k - 1) + ch];
-            }
-            r = r + 0.5f;
-            cl |= (r < 0.0f ? 1u : 0u) << ch;
-        }
+            for (int ch = 0; ch < 3; ++ch) cl |= (sh_clamp(rgb[ch]) ? 1u : 0u) << ch;
         }
         const float dres[3] = {(cl & 1u) ? 0.f : g2[6], (cl & 2u) ? 0.f : g2[7], (cl & 4u) ? 0.f : g2[8]};
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) out.sh_dc[3 * o + ch] = basis[0] * dres[ch];
         float ddx = 0.f, ddy = 0.f, ddz = 0.f;
-        if (lrest) {
-            const float* rest = lrest;
-            float* drest = lrest;
+        // the row's gradient overwrites the row in place
+        if (lrest) sh_dir_grad<true>(nb, in.M_rest, dbx, dby, dbz, lrest, dres, ddx, ddy, ddz, basis, lrest);
+        float dmv[3];
+        sh_dir_to_mean(d, ddx, ddy, ddz, dmv);
 #pragma unroll
-            for (int k = 1; k < 16; ++k) {
-                if (k > in.M_rest) break;
-                if (k < nb) {
-                    const float c0 = rest[3 * (k - 1) + 0], c1 = rest[3 * (k - 1) + 1], c2 = rest[3 * (k - 1) + 2];
-                    drest[3 * (k - 1) + 0] = basis[k] * dres[0];
-                    drest[3 * (k - 1) + 1] = basis[k] * dres[1];
-                    drest[3 * (k - 1) + 2] = basis[k] * dres[2];
-                    const float sdot = c0 * dres[0] + c1 * dres[1] + c2 * dres[2];
-                    ddx += dbx[k] * sdot;
-                    ddy += dby[k] * sdot;
-                    ddz += dbz[k] * sdot;
-                } else {
-                    drest[3 * (k - 1) + 0] = 0.f;
-                    drest[3 * (k - 1) + 1] = 0.f;
-                    drest[3 * (k - 1) + 2] = 0.f;
-                }
-            }
-        }
-        const float dd = x * ddx + y * ddy + z * ddz;
-        dm[0] += (ddx - x * dd) / len;
-        dm[1] += (ddy - y * dd) / len;
-        dm[2] += (ddz - z * dd) / len;
+        for (int k = 0; k < 3; ++k) dm[k] += dmv[k];
     }
     // ---- mean2D (NDC) -> mean3D ----
     {
-        const float hx = Pm[0] * p0 + Pm[4] * p1 + Pm[8] * p2 + Pm[12];
-        const float hy = Pm[1] * p0 + Pm[5] * p1 + Pm[9] * p2 + Pm[13];
-        const float hw = Pm[3] * p0 + Pm[7] * p1 + Pm[11] * p2 + Pm[15];
-        const float mw = 1.0f / (hw + 0.0000001f);
-        const float mw2 = mw * mw;
+        const ClipMean h = clip_mean(Pm, p0, p1, p2);
+        const float mw = h.mw, mw2 = mw * mw;
 #pragma unroll
         for (int k = 0; k < 3; ++k)
-            dm[k] += (Pm[4 * k + 0] * mw - Pm[4 * k + 3] * hx * mw2) * g2[0] +
-                     (Pm[4 * k + 1] * mw - Pm[4 * k + 3] * hy * mw2) * g2[1];
+            dm[k] += (Pm[4 * k + 0] * mw - Pm[4 * k + 3] * h.hx * mw2) * g2[0] +
+                     (Pm[4 * k + 1] * mw - Pm[4 * k + 3] * h.hy * mw2) * g2[1];
     }
     // ---- conic -> cov2D -> (cov3D, view-space mean) ----
     float c3[6], R[9], se[3] = {0.f, 0.f, 0.f};
@@ -402,79 +330,16 @@ __device__ __forceinline__ void preprocess_backward_one(const gsr_camera& cam, c
         for (int k = 0; k < 6; ++k) c3[k] = bi.c3[k];
     } else {
         q = make_float4(bi.c3[0], bi.c3[1], bi.c3[2], bi.c3[3]);
-        const float r = q.x, x = q.y, y = q.z, z = q.w;
-        R[0] = 1.f - 2.f * (y * y + z * z);
-        R[1] = 2.f * (x * y - r * z);
-        R[2] = 2.f * (x * z + r * y);
-        R[3] = 2.f * (x * y + r * z);
-        R[4] = 1.f - 2.f * (x * x + z * z);
-        R[5] = 2.f * (y * z - r * x);
-        R[6] = 2.f * (x * z - r * y);
-        R[7] = 2.f * (y * z + r * x);
-        R[8] = 1.f - 2.f * (x * x + y * y);
-        se[0] = in.smod * bi.s[0];
-        se[1] = in.smod * bi.s[1];
-        se[2] = in.smod * bi.s[2];
-        float L[9];
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) L[3 * i + j] = R[3 * i + j] * se[j];
-        c3[0] = L[0] * L[0] + L[1] * L[1] + L[2] * L[2];
-        c3[1] = L[0] * L[3] + L[1] * L[4] + L[2] * L[5];
-        c3[2] = L[0] * L[6] + L[1] * L[7] + L[2] * L[8];
-        c3[3] = L[3] * L[3] + L[4] * L[4] + L[5] * L[5];
-        c3[4] = L[3] * L[6] + L[4] * L[7] + L[5] * L[8];
-        c3[5] = L[6] * L[6] + L[7] * L[7] + L[8] * L[8];
+        cov3d_from_scale_rot(q, bi.s[0], bi.s[1], bi.s[2], in.smod, R, se, c3);
     }
-    const float tx = V[0] * p0 + V[4] * p1 + V[8] * p2 + V[12];
-    const float ty = V[1] * p0 + V[5] * p1 + V[9] * p2 + V[13];
-    const float tz = V[2] * p0 + V[6] * p1 + V[10] * p2 + V[14];
-    const float Wf = (float)cam.width, Hf = (float)cam.height;
-    const float fx = Wf / (2.0f * cam.tanfovx), fy = Hf / (2.0f * cam.tanfovy);
-    const float limx = 1.3f * cam.tanfovx, limy = 1.3f * cam.tanfovy;
-    const float txtz = tx / tz, tytz = ty / tz;
-    const float cx = fminf(limx, fmaxf(-limx, txtz)) * tz;
-    const float cy = fminf(limy, fmaxf(-limy, tytz)) * tz;
-    const float xmul = (txtz < -limx || txtz > limx) ? 0.f : 1.f;
-    const float ymul = (tytz < -limy || tytz > limy) ? 0.f : 1.f;
-    const float tz2 = tz * tz, tz3 = tz2 * tz;
-    const float J00 = fx / tz, J02 = -(fx * cx) / tz2, J11 = fy / tz, J12 = -(fy * cy) / tz2;
-    float T0[3], T1[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        T0[k] = J00 * V[4 * k + 0] + J02 * V[4 * k + 2];
-        T1[k] = J11 * V[4 * k + 1] + J12 * V[4 * k + 2];
-    }
-    const float S[9] = {c3[0], c3[1], c3[2], c3[1], c3[3], c3[4], c3[2], c3[4], c3[5]};
-    float ST0[3], ST1[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        ST0[i] = S[3 * i + 0] * T0[0] + S[3 * i + 1] * T0[1] + S[3 * i + 2] * T0[2];
-        ST1[i] = S[3 * i + 0] * T1[0] + S[3 * i + 1] * T1[1] + S[3 * i + 2] * T1[2];
-    }
-    const float a0 = ST0[0] * T0[0] + ST0[1] * T0[1] + ST0[2] * T0[2];  // cov2D before the dilation
-    const float a = a0 + 0.3f;
-    const float b = ST0[0] * T1[0] + ST0[1] * T1[1] + ST0[2] * T1[2];
-    const float c0 = ST1[0] * T1[0] + ST1[1] * T1[1] + ST1[2] * T1[2];
-    const float c = c0 + 0.3f;
-    const float det = a * c - b * b;
-    const float dA = g2[2], dB = g2[3], dC = g2[4];
-    const float inv2 = 1.0f / (det * det);
-    float dL_da = inv2 * (-c * c * dA + b * c * dB - b * b * dC);
-    float dL_db = inv2 * (2.f * b * c * dA - (a * c + b * b) * dB + 2.f * a * b * dC);
-    float dL_dc = inv2 * (-b * b * dA + a * b * dB - a * a * dC);
-    if constexpr (AA) {
-        // r's derivatives in their cancellation-free forms: (c0 det - det0 c) / det^2 = (h (c0^2 + b^2) + h^2 c0) / det^2
-        const float h = 0.3f;
-        const float r = (a0 * c0 - b * b) / det;
-        const float coef = sqrtf(fmaxf(0.000025f, r));
-        out.opac[o] = coef * g2[5];
-        const float dL_dr = r <= 0.000025f ? 0.f : (opac_in * g2[5]) / (2.f * coef);
-        dL_da += dL_dr * ((h * (c0 * c0 + b * b) + h * h * c0) * inv2);
-        dL_dc += dL_dr * ((h * (a0 * a0 + b * b) + h * h * a0) * inv2);
-        dL_db += dL_dr * (-2.f * b * (h * (a0 + c0) + h * h) * inv2);
-    }
+    float t[3];
+    view_mean(V, p0, p1, p2, t);
+    const Ewa E = ewa_project(cam, t, c3);
+    const float(&T0)[3] = E.T0, (&T1)[3] = E.T1;
+    const float tz = E.tz, tz2 = E.tz2, tz3 = tz2 * tz, fx = E.fx, fy = E.fy;
+    Cov2dGrad G = cov2d_grad(E, g2[2], g2[3], g2[4]);
+    if constexpr (AA) out.opac[o] = aa_cov2d_grad(E, opac_in, g2[5], G) * g2[5];
+    const float dL_da = G.da, dL_db = G.db, dL_dc = G.dc;
     float dS[6];
     dS[0] = T0[0] * T0[0] * dL_da + T0[0] * T1[0] * dL_db + T1[0] * T1[0] * dL_dc;
     dS[3] = T0[1] * T0[1] * dL_da + T0[1] * T1[1] * dL_db + T1[1] * T1[1] * dL_dc;
@@ -482,20 +347,13 @@ __device__ __forceinline__ void preprocess_backward_one(const gsr_camera& cam, c
     dS[1] = 2.f * T0[0] * T0[1] * dL_da + (T0[0] * T1[1] + T0[1] * T1[0]) * dL_db + 2.f * T1[0] * T1[1] * dL_dc;
     dS[2] = 2.f * T0[0] * T0[2] * dL_da + (T0[0] * T1[2] + T0[2] * T1[0]) * dL_db + 2.f * T1[0] * T1[2] * dL_dc;
     dS[4] = 2.f * T0[1] * T0[2] * dL_da + (T0[1] * T1[2] + T0[2] * T1[1]) * dL_db + 2.f * T1[1] * T1[2] * dL_dc;
-    float dJ00 = 0.f, dJ02 = 0.f, dJ11 = 0.f, dJ12 = 0.f;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const float dT0 = 2.f * ST0[i] * dL_da + ST1[i] * dL_db;
-        const float dT1 = 2.f * ST1[i] * dL_dc + ST0[i] * dL_db;
-        dJ00 += dT0 * V[4 * i + 0];
-        dJ02 += dT0 * V[4 * i + 2];
-        dJ11 += dT1 * V[4 * i + 1];
-        dJ12 += dT1 * V[4 * i + 2];
-    }
-    const float dtx = xmul * (-fx / tz2) * dJ02;
-    const float dty = ymul * (-fy / tz2) * dJ12;
-    float dtz = (-fx / tz2) * dJ00 + (-fy / tz2) * dJ11 + (2.f * fx * cx / tz3) * dJ02 +
-                (2.f * fy * cy / tz3) * dJ12;
+    const TJGrad dj = tj_grad(E, V, G);
+    const float dtx = E.xmul * (-fx / tz2) * dj.dJ02;
+    const float dty = E.ymul * (-fy / tz2) * dj.dJ12;
+    // upstream's in-band factor 2 fx cx / tz^3 outside the guard band too (a clamped cx is treated as a
+    // constant); the camera pass differs here on purpose
+    float dtz = (-fx / tz2) * dj.dJ00 + (-fy / tz2) * dj.dJ11 + (2.f * fx * E.cx / tz3) * dj.dJ02 +
+                (2.f * fy * E.cy / tz3) * dj.dJ12;
     // the depth channel blends v = tz (or 1 / tz): its gradient reaches the mean through tz alone
     if constexpr (AUX == 1) dtz += bi.gz;
     if constexpr (AUX == 2) dtz += -bi.gz / tz2;

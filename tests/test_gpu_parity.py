@@ -525,6 +525,36 @@ def test_backward_equals_blend_plus_preprocess(rast):
             assert torch.equal(v, two[k]), (D, k)
 
 
+def test_preprocess_backward_recomputed_clamp_bits_equal_stored(rast):
+    """B2 with the SH clamp bits it recomputes (a banded forward stores none) = B2 with the bits a
+    full-image forward stored, bit for bit: both evaluate SH -> RGB from the same text
+    (csrc/gsr_gauss_dev.h).  sh_dc is shifted down by 1.75 so that a real share of the channels
+    clamp (on the CPU oracle: 0.46 of the visible Gaussians' channels at degree 3, 0.46 at 1)."""
+    gr, sc = pkg("graphics"), pkg("scene")
+    dev = torch.device("cuda", 0)
+    cam = gr.synthetic_camera(128, 96)
+    assert cam.grid == (8, 6)
+    s = sc.make_scene(cam, 2000, max_sh_degree=3, seed=29)
+    sh_dc = s.sh_dc - np.float32(1.75)
+    dpix = torch.tensor(sc.make_dL_dpix(cam, seed=30), device=dev)
+    for D in (3, 1):
+        fwd = lambda **kw: rast.forward(cam, s.means3D, s.opacities, s.scales, s.rotations, sh_dc, s.sh_rest,
+                                        sh_degree=D, **kw)
+        st_full = fwd()
+        grad2d = rast.backward_blend(st_full, dpix)
+        stored = rast.backward_preprocess(st_full, grad2d)
+        # the input does exercise the clamp: channels whose colour gradient is non-zero and stops at it
+        vis = st_full.radii > 0
+        stopped = (stored["sh_dc"].reshape(-1, 3) == 0) & (grad2d[:, 6:9] != 0) & vis[:, None]
+        share = float(stopped.sum()) / (3.0 * float(vis.sum()))
+        assert 0.1 <= share <= 0.9, (D, share)
+        st_band = fwd(tile_rows=(0, 5))  # the depth keys do not depend on the band
+        recomputed = rast.backward_preprocess(st_band, grad2d)
+        assert stored.keys() == recomputed.keys()
+        for k, v in stored.items():
+            assert torch.equal(v, recomputed[k]), (D, k)
+
+
 def test_5m_forward_backward_properties(rast):
     """BASELINE configs[3]'s workload (5M Gaussians, 1080p, SH3) on one GPU: canonical order,
     K = sum of tiles_touched, transmittance in [0, 1], finite image and gradients, and the same
