@@ -25,6 +25,11 @@
 //                         its span's radii into an LDS bitmap and fetches only the float4 pieces
 //                         that overlap a visible row.
 //  * densify_stats_kernel max_radii2D / grad accumulation / denom for radii > 0.
+//  * mcmc_noise_kernel    the MCMC strategy's per-iteration exploration noise on the means: activations,
+//                         R diag(s^2) R^T and the opacity gate fused, one thread per Gaussian on a
+//                         grid-stride loop, 68 B per Gaussian.
+//  * mcmc_relocate_kernel the opacity / scale a relocated Gaussian and its copies take (refinements
+//                         only): the binomial sum in fp64, one thread per sampled row.
 //  * compact_* + gather_rows_kernel  mask -> ascending index list (wave64 ballot counts,
 //                         block-local scan) and a multi-tensor row gather (prune / clone).
 //
@@ -838,6 +843,100 @@ __global__ __launch_bounds__(256) void densify_stats_kernel(const int* __restric
     den[g] += 1.0f;
 }
 
+// ---------------------------------------------------------------- MCMC densification
+// gsr_mcmc_noise: xyz += Sigma (noise * gate * strength), Sigma = R diag(s^2) R^T from the RAW leaves
+// (the step's activated tensors are stale after the Adam step), gate = 1 / (1 + exp(100 (o - 0.005))).
+// One thread per Gaussian on a grid-stride loop; a thread's five loads are issued before any use.
+// Traffic per Gaussian: xyz 12 + 12, scales 12, rotation 16 (one float4), opacity 4, noise 12 = 68 B.
+constexpr int kNoiseBlock = 256, kNoiseMaxBlocks = 2048;
+
+__global__ __launch_bounds__(kNoiseBlock) void mcmc_noise_kernel(float* __restrict__ xyz, const float* __restrict__ s_raw,
+                                                                 const float4* __restrict__ q_raw,
+                                                                 const float* __restrict__ o_raw,
+                                                                 const float* __restrict__ noise, int P, float strength,
+                                                                 const uint32_t* guard_k, uint32_t guard_cap) {
+    if (guard_tripped(guard_k, guard_cap)) return;
+    const long long stride = (long long)gridDim.x * kNoiseBlock;
+    for (long long g = (long long)blockIdx.x * kNoiseBlock + threadIdx.x; g < P; g += stride) {
+        const float4 r = q_raw[g];
+        const float oraw = o_raw[g];
+        float x[3], sr[3], nz[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            x[k] = xyz[3 * g + k];
+            sr[k] = s_raw[3 * g + k];
+            nz[k] = noise[3 * g + k];
+        }
+        const float o = 1.0f / (1.0f + expf(-oraw));
+        // exp overflows to +inf from o ~ 0.89 on: 1 / (1 + inf) = 0 is the intended gate, and a zero
+        // gate ends the row here -- its xyz keeps its bits, and no inf ever meets a 0
+        const float gate = 1.0f / (1.0f + expf(100.0f * (o - 0.005f)));
+        if (gate == 0.0f) continue;
+        const float n = fmaxf(sqrtf(r.x * r.x + r.y * r.y + r.z * r.z + r.w * r.w), 1e-12f);
+        const float qr = r.x / n, qx = r.y / n, qy = r.z / n, qz = r.w / n;  // w first
+        // general.build_rotation, row-major
+        const float R[3][3] = {{1.f - 2.f * (qy * qy + qz * qz), 2.f * (qx * qy - qr * qz), 2.f * (qx * qz + qr * qy)},
+                               {2.f * (qx * qy + qr * qz), 1.f - 2.f * (qx * qx + qz * qz), 2.f * (qy * qz - qr * qx)},
+                               {2.f * (qx * qz - qr * qy), 2.f * (qy * qz + qr * qx), 1.f - 2.f * (qx * qx + qy * qy)}};
+        const float gs = gate * strength;
+        const float v[3] = {nz[0] * gs, nz[1] * gs, nz[2] * gs};
+        float t[3];  // diag(s^2) R^T v
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float s = expf(sr[k]);
+            t[k] = (s * s) * (R[0][k] * v[0] + R[1][k] * v[1] + R[2][k] * v[2]);
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) xyz[3 * g + k] = x[k] + (R[k][0] * t[0] + R[k][1] * t[1] + R[k][2] * t[2]);
+    }
+}
+
+// gsr_mcmc_relocate.  Binomials C(N, j), N, j <= GSR_MCMC_MAX_RATIO, by Pascal's rule at compile time:
+// every entry is below 2^53 (C(51, 25) ~ 2.5e14), so the doubles are exact.
+struct BinomTable {
+    double c[GSR_MCMC_MAX_RATIO + 1][GSR_MCMC_MAX_RATIO + 1];
+};
+constexpr BinomTable make_binom_table() {
+    BinomTable t{};
+    for (int n = 0; n <= GSR_MCMC_MAX_RATIO; ++n) {
+        t.c[n][0] = 1.0;
+        for (int j = 1; j <= n; ++j) t.c[n][j] = t.c[n - 1][j - 1] + (j <= n - 1 ? t.c[n - 1][j] : 0.0);
+    }
+    return t;
+}
+__constant__ const BinomTable kBinom = make_binom_table();
+
+// With N = the clamped ratio and x = 1 - (1 - o)^(1/N):
+//   D = sum_{k=0..N-1} C(N, k+1) (-1)^k x^(k+1) / sqrt(k+1)
+// (upstream's double sum over i = 1..N collapsed by the hockey-stick identity), new_scale = (o / D) scale,
+// new_opacity = x clamped to [min_opacity, 1 - 2^-24].  The alternating sum loses 1.1e-3 relative in
+// fp32 at o = 1 - 2^-24, N = 51; in fp64 it is good to 2e-12, so x, D and o / D are
+// doubles and each output is rounded to fp32 once.  A row with o <= 0 (nothing to share: x = D = 0)
+// keeps its scale and takes min_opacity.
+__global__ __launch_bounds__(256) void mcmc_relocate_kernel(const float* __restrict__ opac, const float* __restrict__ scales,
+                                                            const int* __restrict__ ratios, int n, float min_opacity,
+                                                            float* __restrict__ new_opac, float* __restrict__ new_scales) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int N = min(max(ratios[i], 1), GSR_MCMC_MAX_RATIO);
+    const double o = (double)opac[i];
+    double x = 0.0, coef = 1.0;
+    if (o > 0.0) {
+        x = -expm1(log1p(-o) / (double)N);  // 1 - (1 - o)^(1/N) without the cancellation at small o
+        double D = 0.0, xp = 1.0;
+        for (int k = 0; k < N; ++k) {
+            xp *= x;
+            const double term = kBinom.c[N][k + 1] * xp / sqrt((double)(k + 1));
+            D += (k & 1) ? -term : term;
+        }
+        coef = o / D;
+    }
+    const double hi = 1.0 - 5.9604644775390625e-8;  // 1 - 2^-24, the largest float below 1
+    new_opac[i] = (float)fmin(fmax(x, (double)min_opacity), hi);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) new_scales[3 * (long long)i + k] = (float)(coef * (double)scales[3 * (long long)i + k]);
+}
+
 // ---------------------------------------------------------------- compaction
 constexpr int kCmpBlock = 256, kCmpPer = 4 * kCmpBlock;
 
@@ -1196,6 +1295,35 @@ int gsr_densify_stats_guarded(const int32_t* radii, const float* dmeans2D, int32
     if (!radii || !dmeans2D || !max_radii2D || !grad_accum || !denom) return set_error(-1, "densify_stats: null tensor");
     hipLaunchKernelGGL(densify_stats_kernel, dim3((P + 255) / 256), dim3(256), 0, (hipStream_t)stream, radii, dmeans2D, P,
                        max_radii2D, grad_accum, denom, guard_k, guard_cap);
+    return (int)hipGetLastError();
+}
+
+int gsr_mcmc_noise(float* xyz, const float* scale_raw, const float* rot_raw, const float* opac_raw, const float* noise,
+                   int32_t P, float strength, const uint32_t* guard_k, uint32_t guard_cap, void* stream) {
+    if (P < 0) return set_error(-1, "mcmc_noise: negative P");
+    if (!(strength >= 0.0f) || std::isinf(strength)) return set_error(-1, "mcmc_noise: strength must be finite and >= 0");
+    if (P == 0) return 0;
+    if (!xyz || !scale_raw || !rot_raw || !opac_raw || !noise) return set_error(-1, "mcmc_noise: null pointer");
+    if (reinterpret_cast<uintptr_t>(rot_raw) & 15) return set_error(-1, "mcmc_noise: rotations must be 16-byte aligned");
+    for (const void* p : {(const void*)xyz, (const void*)scale_raw, (const void*)opac_raw, (const void*)noise})
+        if (reinterpret_cast<uintptr_t>(p) & 3) return set_error(-1, "mcmc_noise: tensors must be 4-byte aligned");
+    if (strength == 0.0f) return 0;  // a zero displacement: xyz keeps its bytes
+    const long long want = ((long long)P + kNoiseBlock - 1) / kNoiseBlock;
+    const int nb = (int)(want < kNoiseMaxBlocks ? want : kNoiseMaxBlocks);
+    hipLaunchKernelGGL(mcmc_noise_kernel, dim3(nb), dim3(kNoiseBlock), 0, (hipStream_t)stream, xyz, scale_raw,
+                       reinterpret_cast<const float4*>(rot_raw), opac_raw, noise, P, strength, guard_k, guard_cap);
+    return (int)hipGetLastError();
+}
+
+int gsr_mcmc_relocate(const float* opacities, const float* scales, const int32_t* ratios, int32_t n, float min_opacity,
+                      float* new_opacities, float* new_scales, void* stream) {
+    if (n < 0) return set_error(-1, "mcmc_relocate: negative n");
+    if (!(min_opacity > 0.0f && min_opacity < 1.0f)) return set_error(-1, "mcmc_relocate: min_opacity must lie in (0, 1)");
+    if (n == 0) return 0;
+    if (!opacities || !scales || !ratios || !new_opacities || !new_scales)
+        return set_error(-1, "mcmc_relocate: null pointer");
+    hipLaunchKernelGGL(mcmc_relocate_kernel, dim3((unsigned)(((long long)n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, opacities, scales,
+                       ratios, n, min_opacity, new_opacities, new_scales);
     return (int)hipGetLastError();
 }
 

@@ -59,7 +59,8 @@ CAMERA_GRAD_FLOATS = 36  # gsr.h GSR_CAMERA_GRAD_FLOATS: dL/dviewmatrix[16], dL/
 TRAIN_EXPORTS = ["gsr_activate", "gsr_loss_scratch_bytes", "gsr_loss_forward", "gsr_loss_backward", "gsr_adam_step",
                  "gsr_adam_step_guarded", "gsr_adam_step_sparse", "gsr_densify_stats", "gsr_densify_stats_guarded", "gsr_compact_scratch_bytes", "gsr_compact_index", "gsr_gather_rows",
                  "gsr_knn_scratch_bytes", "gsr_knn_mean_dist2", "gsr_depth_loss_scratch_bytes", "gsr_depth_loss",
-                 "gsr_exposure_scratch_bytes", "gsr_exposure_forward", "gsr_exposure_backward"]
+                 "gsr_exposure_scratch_bytes", "gsr_exposure_forward", "gsr_exposure_backward",
+                 "gsr_mcmc_noise", "gsr_mcmc_relocate"]
 COMM_EXPORTS = ["gsr_comm_unique_id", "gsr_comm_init", "gsr_comm_destroy", "gsr_comm_size", "gsr_comm_all_to_all",
                 "gsr_comm_all_gather", "gsr_comm_all_reduce_i64"]  # include/gsr/gsr_comm.h
 COMM_ID_BYTES = 128
@@ -68,6 +69,7 @@ DEPTH_RAW, DEPTH_NORMALIZED = range(2)  # gsr_train.h GSR_DEPTH_*
 EXPOSURE_CLAMP = 1  # gsr_train.h GSR_EXPOSURE_CLAMP: clamp the exposed image to [0, 1]
 ADAM_MAX_GROUPS = 8
 GATHER_MAX = 24
+MCMC_MAX_RATIO = 51  # gsr_train.h GSR_MCMC_MAX_RATIO: the largest number of Gaussians sharing one relocated row
 STAGES = ["preprocess", "depth_sort", "scan", "duplicate", "tile_sort", "finalize", "blend_fwd", "blend_bwd",
           "preprocess_bwd", "gather_grad2d", "misc", "exchange"]
 
@@ -251,6 +253,10 @@ def load_hip() -> ctypes.CDLL:
         L.gsr_densify_stats.argtypes = [vp, vp, i32, vp, vp, vp, vp]
         L.gsr_densify_stats_guarded.restype = ctypes.c_int
         L.gsr_densify_stats_guarded.argtypes = [vp, vp, i32, vp, vp, vp, vp, ctypes.c_uint32, vp]
+        L.gsr_mcmc_noise.restype = ctypes.c_int
+        L.gsr_mcmc_noise.argtypes = [vp, vp, vp, vp, vp, i32, f32, vp, ctypes.c_uint32, vp]
+        L.gsr_mcmc_relocate.restype = ctypes.c_int
+        L.gsr_mcmc_relocate.argtypes = [vp, vp, vp, i32, f32, vp, vp, vp]
         L.gsr_compact_scratch_bytes.restype = ctypes.c_size_t
         L.gsr_compact_scratch_bytes.argtypes = [i32]
         L.gsr_compact_index.restype = ctypes.c_int

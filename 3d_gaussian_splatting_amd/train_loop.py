@@ -11,7 +11,9 @@ then the fused Adam step -- with the OptimizationParams defaults of src/argument
 No host synchronisation inside an iteration except the densification read-backs; the loss is
 read back only at the log points.  A scene that carries per-view depth targets adds upstream's
 depth term to every iteration (``GaussianTrainer.step(gt_depth=...)``); ``opt.train_exposure`` trains
-one exposure row per view beside the Gaussians (``step(view_index=...)``).
+one exposure row per view beside the Gaussians (``step(view_index=...)``);
+``opt.densify_strategy = "mcmc"`` replaces the densify / prune / reset schedule by relocation, growth
+to ``cap_max`` and the per-step noise (``GaussianTrainer.mcmc_refine``), at the same refinement iterations.
 
 The scene: ground-truth images rendered by the same rasterizer from a procedural cloud of
 Gaussians (a textured ground disc and a few object blobs, SH degree 1) seen by cameras on an
@@ -199,6 +201,9 @@ def write_scene(path: str, scene: LoopScene, iterations: int, opt: OptimizationP
     if opt.train_poses:
         raise ValueError("write_scene: the GSRLOOP1 file has no pose switch (the C++ loop trains without pose "
                          "refinement); pass opt.train_poses = False")
+    if opt.densify_strategy != "default":
+        raise ValueError("write_scene: the GSRLOOP1 file has no densification switch (the C++ loop keeps the "
+                         "default clone / split / prune strategy); pass opt.densify_strategy = \"default\"")
     views = view_sequence(len(scene.cams), iterations, seed) if views is None else np.asarray(views, np.int32)
     H, W = int(scene.gts[0].shape[1]), int(scene.gts[0].shape[2])
     with open(path, "wb") as f:

@@ -29,7 +29,9 @@ six groups, activation backward fused; with opt.train_exposure gsr_exposure_forw
 gsr_exposure_backward around the loss and one more guarded Adam launch for the per-view exposure
 tensor); with a depth target (``step(gt_depth=...)``, upstream
 3DGS's depth regulariser -- the reference has none) the render is gsr_forward_aux /
-gsr_backward_aux with gsr_depth_loss between them.  No host synchronisation inside ``step`` (the loss
+gsr_backward_aux with gsr_depth_loss between them; with opt.densify_strategy = "mcmc" (gsplat's
+MCMCStrategy -- neither upstream nor the reference has it) no gsr_densify_stats, gsr_mcmc_noise after
+the Adam step and gsr_mcmc_relocate inside the refinements (``mcmc_refine``).  No host synchronisation inside ``step`` (the loss
 stays on the device); densification (every ``densification_interval`` iterations) reads
 counts back.  The forward's binning runs under a capacity bound (``BinningCapacity``), so K is
 not read back either: the first render after a change in the point set is sized exactly (one
@@ -115,9 +117,24 @@ class OptimizationParams:
     pose_lr_final: float = 1e-6
     pose_lr_delay_steps: int = 0
     pose_lr_delay_mult: float = 0.0
+    # "default": upstream's clone / split / prune on a gradient threshold with the opacity reset;
+    # "mcmc" (gsplat's MCMCStrategy, Kheradmand et al. 2024; neither upstream 3DGS nor the reference
+    # has it): dead Gaussians are relocated onto live ones, the set grows by mcmc_growth per
+    # refinement up to the hard limit cap_max and then keeps that size, no opacity reset, a
+    # covariance-shaped noise on the means every step (gsr_mcmc_noise, strength noise_lr x the
+    # scheduled xyz rate) and two L1 regularisers, opacity_reg x mean(opacity) and scale_reg x
+    # mean(scale).  noise_lr, the regularisers, mcmc_min_opacity and mcmc_growth are gsplat's defaults
+    densify_strategy: str = "default"
+    cap_max: int = 1_000_000
+    noise_lr: float = 5e5
+    opacity_reg: float = 0.01
+    scale_reg: float = 0.01
+    mcmc_min_opacity: float = 0.005
+    mcmc_growth: float = 1.05
 
 
 OPTIMIZER_TYPES = ("default", "sparse_adam")
+DENSIFY_STRATEGIES = ("default", "mcmc")
 
 
 class PoseState:
@@ -324,6 +341,40 @@ class TrainKernels:
         gk, gcap = _guard(guard)
         self._check(self.L.gsr_densify_stats_guarded(_p(radii), _p(dmeans2D), P, _p(max_radii2D), _p(grad_accum),
                                                      _p(denom), gk, gcap, _stream(self.device)), "gsr_densify_stats")
+
+    def _f32_rows(self, what, name, t, shape):
+        if not (t.is_contiguous() and t.dtype == torch.float32 and t.device == self.device
+                and tuple(t.shape) == tuple(shape)):
+            raise ValueError(f"{what}: {name} must be a contiguous f32 {tuple(shape)} tensor on {self.device}")
+
+    def mcmc_noise(self, xyz, scale_raw, rot_raw, opac_raw, noise, strength, guard=None):
+        """gsr_mcmc_noise, in place on xyz (P, 3): xyz += R diag(s^2) R^T (noise * gate * strength) from
+        the raw leaves scale_raw (P, 3), rot_raw (P, 4), opac_raw (P, 1) or (P,), with noise (P, 3)
+        standard-normal floats the caller drew.  guard as adam_step."""
+        P = int(xyz.shape[0])
+        self._f32_rows("mcmc_noise", "xyz", xyz, (P, 3))
+        self._f32_rows("mcmc_noise", "scale_raw", scale_raw, (P, 3))
+        self._f32_rows("mcmc_noise", "rot_raw", rot_raw, (P, 4))
+        self._f32_rows("mcmc_noise", "opac_raw", opac_raw, (P, 1) if opac_raw.dim() == 2 else (P,))
+        self._f32_rows("mcmc_noise", "noise", noise, (P, 3))
+        gk, gcap = _guard(guard)
+        self._check(self.L.gsr_mcmc_noise(_p(xyz), _p(scale_raw), _p(rot_raw), _p(opac_raw), _p(noise), P,
+                                          float(strength), gk, gcap, _stream(self.device)), "gsr_mcmc_noise")
+
+    def mcmc_relocate(self, opacities, scales, ratios, min_opacity):
+        """gsr_mcmc_relocate on n sampled rows: activated opacities (n,), scales (n, 3) and int32
+        ratios (n,) (how many Gaussians share the row, clamped to [1, native.MCMC_MAX_RATIO]) ->
+        (new_opacities (n,), new_scales (n, 3))."""
+        n = int(opacities.shape[0])
+        self._f32_rows("mcmc_relocate", "opacities", opacities, (n,))
+        self._f32_rows("mcmc_relocate", "scales", scales, (n, 3))
+        if not (ratios.is_contiguous() and ratios.dtype == torch.int32 and ratios.device == self.device
+                and tuple(ratios.shape) == (n,)):
+            raise ValueError(f"mcmc_relocate: ratios must be a contiguous int32 ({n},) tensor on {self.device}")
+        new_o, new_s = torch.empty_like(opacities), torch.empty_like(scales)
+        self._check(self.L.gsr_mcmc_relocate(_p(opacities), _p(scales), _p(ratios), n, float(min_opacity), _p(new_o),
+                                             _p(new_s), _stream(self.device)), "gsr_mcmc_relocate")
+        return new_o, new_s
 
     def compact_index(self, mask: torch.Tensor) -> torch.Tensor:
         """Ascending int32 indices of the nonzero entries of a bool / uint8 mask (one D2H read)."""
@@ -587,6 +638,19 @@ class GaussianTrainer:
         """GaussianModel::setup (gaussian_model.cpp:316-352)."""
         if opt.optimizer_type not in OPTIMIZER_TYPES:
             raise ValueError(f"optimizer_type must be one of {OPTIMIZER_TYPES}, not {opt.optimizer_type!r}")
+        if opt.densify_strategy not in DENSIFY_STRATEGIES:
+            raise ValueError(f"densify_strategy must be one of {DENSIFY_STRATEGIES}, not {opt.densify_strategy!r}")
+        if opt.densify_strategy == "mcmc":
+            for name in ("noise_lr", "opacity_reg", "scale_reg"):
+                v = getattr(opt, name)
+                if not (math.isfinite(v) and v >= 0.0):
+                    raise ValueError(f"{name} must be a finite, non-negative number, not {v!r}")
+            if not 0.0 < opt.mcmc_min_opacity < 1.0:
+                raise ValueError(f"mcmc_min_opacity must lie in (0, 1), not {opt.mcmc_min_opacity!r}")
+            if not (math.isfinite(opt.mcmc_growth) and opt.mcmc_growth >= 1.0):
+                raise ValueError(f"mcmc_growth must be a finite number >= 1, not {opt.mcmc_growth!r}")
+            if int(opt.cap_max) < 1:
+                raise ValueError(f"cap_max must be positive, not {opt.cap_max!r}")
         for name in ("pose_lr_init", "pose_lr_final", "pose_lr_delay_mult"):
             v = getattr(opt, name)
             if not (math.isfinite(v) and v >= 0.0):
@@ -760,8 +824,20 @@ class GaussianTrainer:
         if the copy has not landed) or at flush_poses() -- never opportunistically, so step() still has
         no host synchronisation in steady state and a run does not depend on timing.  An update whose
         render overflowed its binning bound is dropped.  The dict gains "camera" (the corrected camera)
-        and "dL_dcamera" (36 floats, device).  Without it the iteration is unchanged, call for call."""
+        and "dL_dcamera" (36 floats, device).  Without it the iteration is unchanged, call for call.
+
+        With opt.densify_strategy = "mcmc" (gsplat's MCMCStrategy) the iteration keeps no densification
+        statistics and never prunes or resets opacities.  The two L1 regularisers enter as constants on
+        the rasterizer's gradients with respect to the ACTIVATED values: opacity_reg / P on every
+        dL/dopacity and scale_reg / (3 P) on every dL/dscale (regularizer_values() gives the terms
+        themselves).  When densify_from_iter < iteration < densify_until_iter and iteration %
+        densification_interval == 0 (and densify), mcmc_refine() runs in front of the optimizer step;
+        it changes which Gaussian a row holds, so that iteration steps no group and the binning bound
+        is reset, as on a densify iteration of the default strategy.  After the optimizer step
+        gsr_mcmc_noise moves the means by noise drawn from the trainer's generator, at strength
+        noise_lr x the scheduled xyz rate, under the same device guard -- on refine iterations too."""
         opt = self.opt
+        mcmc = opt.densify_strategy == "mcmc"
         posed = opt.train_poses
         if posed:
             if self.poses is None:
@@ -822,7 +898,18 @@ class GaussianTrainer:
         if self.params["f_rest"].shape[1]:
             grads["f_rest"] = g["sh_rest"]
         replaced = set()
-        if iteration < opt.densify_until_iter:
+        if mcmc:
+            P = self.num_points
+            if opt.opacity_reg:
+                grads["opacity"].add_(opt.opacity_reg / P)
+            if opt.scale_reg:
+                grads["scaling"].add_(opt.scale_reg / (3 * P))
+            if (densify and opt.densify_from_iter < iteration < opt.densify_until_iter
+                    and iteration % opt.densification_interval == 0):
+                self.mcmc_refine()
+                self.binning.reset()
+                replaced.update(GROUPS)
+        elif iteration < opt.densify_until_iter:
             self.k.densify_stats(st.radii, g["means2D"], self.max_radii2D, self.xyz_gradient_accum, self.denom,
                                  guard=self._guard)
             if densify:
@@ -843,6 +930,11 @@ class GaussianTrainer:
                 self.k.adam_step([dict(param=self.exposure, grad=exposure_grad, exp_avg=self.exposure_exp_avg,
                                        exp_avg_sq=self.exposure_exp_avg_sq, act=native.ACT_NONE,
                                        step=self.exposure_step, lr=self.exposure_lr)], guard=self._guard)
+            if mcmc:
+                p = self.params
+                noise = torch.randn((self.num_points, 3), dtype=torch.float32, device=self.device, generator=self.gen)
+                self.k.mcmc_noise(p["xyz"], p["scaling"], p["rotation"], p["opacity"], noise,
+                                  opt.noise_lr * self.lr["xyz"], guard=self._guard)
         out ={"stats": stats, "radii": st.radii, "state": st, "image": st.color, "num_points": self.num_points}
         if supervised:
             out.update(depth_stats=depth_stats, depth=st.depth, alpha=st.alpha, dL_ddepth=dd)
@@ -867,6 +959,74 @@ class GaussianTrainer:
             self.k.adam_step(groups, guard=self._guard, visibility=visibility)
         elif groups:
             self.k.adam_step(groups, guard=self._guard)
+
+    # ---------------------------------------------------------------- densification (MCMC)
+    def regularizer_values(self) -> dict:
+        """The two regularisation terms of the "mcmc" strategy at the current parameters, as upstream
+        writes them: opacity_reg * mean(sigmoid(opacity)) and scale_reg * mean(exp(scaling)).  step()
+        applies their gradients only; this reads the values back (one host synchronisation)."""
+        o = torch.sigmoid(self.params["opacity"]).mean()
+        s = torch.exp(self.params["scaling"]).mean()
+        return {"opacity_reg": self.opt.opacity_reg * float(o), "scale_reg": self.opt.scale_reg * float(s)}
+
+    def _mcmc_sample(self, probs: torch.Tensor, n: int) -> torch.Tensor:
+        """n indices drawn with probability proportional to probs (>= 0), with replacement, by inverse
+        CDF in float64 from the trainer's generator.  (torch.multinomial stops at 2^24 categories.)
+        A row of probability 0 repeats its predecessor's CDF value and is never the first above u."""
+        cdf = torch.cumsum(probs.to(torch.float64), 0)
+        u = torch.rand(n, dtype=torch.float64, device=self.device, generator=self.gen) * cdf[-1]
+        return torch.searchsorted(cdf, u, right=True).clamp_(max=int(probs.numel()) - 1)
+
+    def _mcmc_relocate_sources(self, src: torch.Tensor):
+        """The rows `src` (int64, repeats allowed) are each about to be shared with one more Gaussian
+        per occurrence: gsr_mcmc_relocate on their activated opacity and scales, written back in raw
+        form (logit, log) in place, and both Adam moments of those rows zeroed in all six groups."""
+        p = self.params
+        counts = torch.bincount(src, minlength=self.num_points)
+        ratios = (counts[src] + 1).to(torch.int32).contiguous()
+        o = torch.sigmoid(p["opacity"][src, 0]).contiguous()
+        s = torch.exp(p["scaling"][src]).contiguous()
+        new_o, new_s = self.k.mcmc_relocate(o, s, ratios, self.opt.mcmc_min_opacity)
+        # repeated sources carry equal values (same row, same ratio): the scatter's order is immaterial
+        p["opacity"][src, 0] = torch.log(new_o / (1 - new_o))  # inverse_sigmoid; new_o <= 1 - 2^-24
+        p["scaling"][src] = torch.log(new_s)
+        for k in GROUPS:
+            self.exp_avg[k][src] = 0.0
+            self.exp_avg_sq[k][src] = 0.0
+
+    def mcmc_refine(self) -> dict:
+        """One refinement of the "mcmc" strategy (gsplat's MCMCStrategy._relocate_gs then _add_new_gs).
+
+        1. dead = sigmoid(opacity) <= mcmc_min_opacity.  With dead and live rows both present: as many
+           sources as dead rows are sampled from the live rows with probability proportional to their
+           opacity (with replacement), the sources take the relocated opacity / scales (zeroed moments),
+           and every dead row becomes a copy of its source's six parameters, in place.  The dead rows
+           keep their moments, as upstream.
+        2. n_new = max(0, min(cap_max, int(mcmc_growth * P)) - P) sources are sampled from all rows
+           in the same way and relocated, and their copies are appended with zero moments.
+        Once P == cap_max step 2 does nothing and no parameter or moment tensor is replaced again.
+        Returns {"relocated": n_dead or 0, "added": n_new}; reads counts back (host synchronisation)."""
+        opt = self.opt
+        p = self.params
+        P = self.num_points
+        o = torch.sigmoid(p["opacity"][:, 0])
+        dead = o <= opt.mcmc_min_opacity
+        dead_idx = torch.nonzero(dead)[:, 0]
+        n_dead = int(dead_idx.numel())
+        relocated = 0
+        if 0 < n_dead < P:
+            live_idx = torch.nonzero(~dead)[:, 0]
+            src = live_idx[self._mcmc_sample(o[live_idx], n_dead)]
+            self._mcmc_relocate_sources(src)
+            for k in GROUPS:
+                p[k][dead_idx] = p[k][src]
+            relocated = n_dead
+        n_new = max(0, min(int(opt.cap_max), int(opt.mcmc_growth * P)) - P)
+        if n_new > 0:
+            src = self._mcmc_sample(torch.sigmoid(p["opacity"][:, 0]), n_new)
+            self._mcmc_relocate_sources(src)
+            self._append({k: p[k][src] for k in GROUPS})
+        return {"relocated": relocated, "added": n_new}
 
     # ---------------------------------------------------------------- densification (upstream)
     def _append(self, new: dict):

@@ -40,6 +40,15 @@
  *   gsr_gather_rows           (upstream densification; the reference declares only the stats
  *                             tensors): index list from a mask, then one multi-tensor row
  *                             gather for parameters, Adam moments and statistics.
+ *   gsr_mcmc_noise         <- gsplat's inject_noise_to_position (MCMCStrategy, "3D Gaussian Splatting
+ *                             as Markov Chain Monte Carlo", Kheradmand et al. 2024): the per-step,
+ *                             covariance-shaped, opacity-gated noise on the means, with the
+ *                             activations and the covariance fused in.  Neither upstream 3DGS nor
+ *                             the reference has it.
+ *   gsr_mcmc_relocate      <- gsplat's `relocation` kernel (compute_relocation): the opacity and
+ *                             scale that a Gaussian and the copies teleported onto it take so that
+ *                             together they render as the one did.  Neither upstream 3DGS nor the
+ *                             reference has it.
  */
 #ifndef GSR_GSR_TRAIN_H
 #define GSR_GSR_TRAIN_H
@@ -165,6 +174,33 @@ int gsr_densify_stats(const int32_t* radii, const float* dmeans2D, int32_t P, fl
 int gsr_densify_stats_guarded(const int32_t* radii, const float* dmeans2D, int32_t P, float* max_radii2D,
                               float* grad_accum, float* denom, const uint32_t* guard_k, uint32_t guard_cap,
                               void* stream);
+
+/* MCMC densification, the per-iteration noise: for each of the P Gaussians, from the RAW leaves,
+ *   s = exp(scale_raw), q = rot_raw / max(|rot_raw|, 1e-12) (w first), R = R(q), o = sigmoid(opac_raw),
+ *   gate = 1 / (1 + exp(100 (o - 0.005)))       (upstream's op_sigmoid(1 - o, k = 100, x0 = 0.995))
+ *   xyz += R diag(s^2) R^T (noise * gate * strength)
+ * noise: P x 3 standard-normal floats the caller drew (the kernel is a pure function of its inputs);
+ * strength = noise_lr * the scheduled xyz rate, finite and >= 0.  The gate reaches exactly 0 for
+ * opaque Gaussians (exp overflows to +inf, 1 / (1 + inf) = 0); such a row keeps the bits of its xyz,
+ * and so does every row at strength 0 (no launch).  rot_raw 16-byte aligned, the others 4.  Skipped
+ * on the device when *guard_k > guard_cap (as gsr_adam_step_guarded; NULL: never skipped).  P == 0:
+ * returns 0.  One launch, no scratch, no atomics; 68 B of traffic per Gaussian. */
+int gsr_mcmc_noise(float* xyz, const float* scale_raw, const float* rot_raw, const float* opac_raw,
+                   const float* noise, int32_t P, float strength,
+                   const uint32_t* guard_k, uint32_t guard_cap, void* stream);
+
+/* MCMC densification, the relocation: row i (ACTIVATED opacity o, scale, of n sampled rows) is about
+ * to be shared by N = ratios[i] clamped to [1, GSR_MCMC_MAX_RATIO] Gaussians.  With
+ *   x = 1 - (1 - o)^(1/N)
+ *   D = sum_{i=1..N} sum_{k=0..i-1} C(i-1, k) (-1)^k x^(k+1) / sqrt(k+1)
+ *     = sum_{k=0..N-1} C(N, k+1) (-1)^k x^(k+1) / sqrt(k+1)
+ *   new_scales = (o / D) scales,  new_opacities = min(max(x, min_opacity), 1 - 2^-24).
+ * x, D and o / D are evaluated in fp64 (binomials from a table inside the library) and each output
+ * is rounded to fp32 once.  A row with o <= 0 keeps its scale and takes min_opacity.  min_opacity in
+ * (0, 1); n == 0: returns 0.  The outputs must not overlap the inputs (not checked). */
+#define GSR_MCMC_MAX_RATIO 51
+int gsr_mcmc_relocate(const float* opacities, const float* scales, const int32_t* ratios, int32_t n,
+                      float min_opacity, float* new_opacities, float* new_scales, void* stream);
 
 /* Stream compaction: idx_out[0 .. count) = the i with mask[i] != 0, ascending; *count_out
  * (device int32).  scratch: gsr_compact_scratch_bytes(n). */
