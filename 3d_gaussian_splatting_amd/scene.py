@@ -69,7 +69,13 @@ def make_scene(cam: RasterCamera, P: int, max_sh_degree: int = 3, seed: int = 0,
     z ~ U[2,12]; x = (2u-1) 1.1 z tanfovx; y = (2u-1) 1.1 z tanfovy;
     log s_k = log(3 px * z / f_x) + 0.5 n;  rotation raw ~ N(0,1)^4 (normalised);
     opacity raw = clamp(N(0, 1.5), -6, 4.5) (sigmoid <= 0.989 < 0.99: alpha clamp never hit);
-    SH dc ~ N(0, 0.3), rest ~ N(0, 0.05)."""
+    SH dc ~ N(0, 0.3), rest ~ N(0, 0.05).
+
+    An easy scene by construction, under synthetic_camera (R = I, T = 0) in particular: the colour sum
+    0.28 dc + 0.5 + ... clamps at 0 only about six sigma out, so the SH clamp is in effect never hit
+    either; |x / z| <= 1.1 tan(fov) stays inside the 1.3 tan(fov) guard band (xmul = ymul = 1 always);
+    z >= 2 is far from the 0.2 near plane.  The branches it cannot reach are tested on the edge scene
+    (tests/pose_reference.py make_case(edge=True))."""
     u = uniform(seed, _S_MEANS, 3 * P).reshape(P, 3)
     z = 2.0 + 10.0 * u[:, 2]
     x = (2.0 * u[:, 0] - 1.0) * 1.1 * z * cam.tanfovx

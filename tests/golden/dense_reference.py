@@ -172,9 +172,16 @@ def geometry_f32(cam, means, opac, scales=None, rots=None, cov3D=None, scale_mod
         return dict(radius=radius, rect=rect, visible=visible, depth=tz)
 
 
-def render(cam, pre, geom, bg, gid_order=None):
+def render(cam, pre, geom, bg, gid_order=None, alpha_clamp_grad="autograd"):
     """Dense front-to-back compositing over every pixel, Gaussians in (depth_bits, gid)
-    order, restricted to pixels whose tile lies in the Gaussian's rect."""
+    order, restricted to pixels whose tile lies in the Gaussian's rect.
+
+    alpha_clamp_grad: the gradient through alpha = min(0.99, o G) where it saturates.  "autograd":
+    zero, the derivative of the clamp (nothing the golden fixtures render reaches it).  "upstream":
+    the gradient passes straight through, d alpha = d(o G) with the unclamped o G, as the blend
+    backward of the kernels and of the CPU oracle has it; the value is the clamped one either way."""
+    if alpha_clamp_grad not in ("autograd", "upstream"):
+        raise ValueError(f"alpha_clamp_grad: {alpha_clamp_grad!r}")
     dtype = pre["xy"].dtype
     W, H = cam.width, cam.height
     vis = geom["visible"]
@@ -201,7 +208,10 @@ def render(cam, pre, geom, bg, gid_order=None):
         co = pre["conic"][g]
         power = -0.5 * (co[0] * dx * dx + co[2] * dy * dy) - co[1] * dx * dy
         Gv = torch.exp(power)
-        alpha = torch.clamp_max(pre["opacity"][g] * Gv, 0.99)
+        oG = pre["opacity"][g] * Gv
+        alpha = torch.clamp_max(oG, 0.99)
+        if alpha_clamp_grad == "upstream":
+            alpha = oG + (alpha - oG).detach()
         with torch.no_grad():
             a32 = alpha.to(torch.float32)
             keep = inr & alive & (power.to(torch.float32) <= 0) & (a32 >= 1.0 / 255.0)

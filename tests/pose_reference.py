@@ -8,6 +8,10 @@ the kernels' f32 summation error is measured against.  It adds what dense_refere
 the anti-aliased opacity o' = o sqrt(max(0.000025, det0 / det)) and the depth channel's value
 v = tz (or 1 / tz).  The three fields are independent inputs, exactly as the kernels read them.
 dense_reference.render, geometry_f32 and sh_basis are reused by import.
+
+It is also the float64 reference of the leaf gradients on the edge scene (make_case(edge=True),
+tests/test_edge_reference.py): float64 leaf tensors passed as inputs stay in the graph, and
+band_grad="upstream" gives B2's convention outside the guard band instead of the camera kernel's.
 """
 from __future__ import annotations
 
@@ -23,11 +27,18 @@ def t64(a):
 
 
 def preprocess(cam, means, opac, scales=None, rots=None, sh_dc=None, sh_rest=None, D=0, colors=None, cov3D=None,
-               scale_mod=1.0, antialias=False, inverse_depth=False):
+               scale_mod=1.0, antialias=False, inverse_depth=False, band_grad="forward"):
     """The per-Gaussian quantities the blend consumes, differentiable in the expanded camera leaves
-    "V", "Pm", "campos" (returned in the dict).  Keys as dense_reference.preprocess (xy, depth, conic,
-    opacity, rgb) plus "ndc", "value" (the depth channel's v), "sh_sum" (res before the clamp, or None)
-    and "txtz" / "tytz" (the guard-band arguments)."""
+    "V", "Pm", "campos" (returned in the dict) and in any float64 leaf passed as an input.  Keys as
+    dense_reference.preprocess (xy, depth, conic, opacity, rgb) plus "ndc", "value" (the depth channel's
+    v), "sh_sum" (res before the clamp, or None) and "txtz" / "tytz" (the guard-band arguments).
+
+    band_grad: the derivative of J's cx = clamp(tx / tz, +-1.3 tan(fov)) tz (and cy) outside the guard
+    band.  "forward": the forward's own (cx = +-lim tz, dJ02/dtz = fx cx / tz^3), what the camera kernel
+    computes.  "upstream": the clamped cx a constant (dL/dtx gets nothing, dJ02/dtz keeps the in-band
+    2 fx cx / tz^3), what B2 and the CPU oracle compute.  The values are the same."""
+    if band_grad not in ("forward", "upstream"):
+        raise ValueError(f"band_grad: {band_grad!r}")
     means, opac, scales, rots, sh_dc, sh_rest, colors, cov3D = (t64(a) for a in (means, opac, scales, rots, sh_dc,
                                                                                  sh_rest, colors, cov3D))
     P = means.shape[0]
@@ -60,6 +71,9 @@ def preprocess(cam, means, opac, scales=None, rots=None, sh_dc=None, sh_rest=Non
     txtz, tytz = tx / tz, ty / tz
     cx = torch.clamp(txtz, -limx, limx) * tz
     cy = torch.clamp(tytz, -limy, limy) * tz
+    if band_grad == "upstream":
+        cx = torch.where(txtz.detach().abs() > limx, cx.detach(), tx)
+        cy = torch.where(tytz.detach().abs() > limy, cy.detach(), ty)
     zero = torch.zeros_like(tz)
     J = torch.stack([fx / tz, zero, -(fx * cx) / (tz * tz), zero, fy / tz, -(fy * cy) / (tz * tz)],
                     dim=1).reshape(-1, 2, 3)
@@ -138,14 +152,45 @@ def posed_camera(width=96, height=64, fovx_deg=60.0):
     return pkg("train_loop").look_at_camera((1.7, -0.9, -3.1), (0.3, 0.2, 0.4), math.radians(fovx_deg), width, height)
 
 
-def make_case(P, D=3, colors=False, cov3D=False, seed=0, cam=None, behind=True, band=True):
+def rolled_camera(width=96, height=64, fovx_deg=60.0, roll_deg=25.0):
+    """posed_camera()'s centre and target, rolled about the optical axis.  A look-at camera whose up is
+    the world's y has a right vector without a y component, so posed_camera()'s viewmatrix[4] is zero
+    (-9e-18); after the roll none of the nine rotation entries is (the least is 0.23 in magnitude), and
+    a transposed or mis-indexed V[4k+i] moves every quantity."""
+    import math
+
+    import numpy as np
+
+    from conftest import pkg
+    c, target = np.array([1.7, -0.9, -3.1]), np.array([0.3, 0.2, 0.4])
+    f = target - c
+    f /= np.linalg.norm(f)
+    d = np.array([0.0, 1.0, 0.0])
+    y = d - f * (d @ f)
+    y /= np.linalg.norm(y)
+    x = np.cross(y, f)
+    cr, sr = math.cos(math.radians(roll_deg)), math.sin(math.radians(roll_deg))
+    Rt = np.stack([cr * x + sr * y, cr * y - sr * x, f])  # world -> camera rows
+    fovx = math.radians(fovx_deg)
+    fovy = 2.0 * math.atan(math.tan(fovx / 2.0) * height / width)
+    return pkg("graphics").make_camera(Rt.T, -Rt @ c, fovx, fovy, width, height)
+
+
+def make_case(P, D=3, colors=False, cov3D=False, seed=0, cam=None, behind=True, band=True, edge=False):
     """P Gaussians in front of `cam` (default posed_camera()), scattered over its field of view and a
     depth range, f32 numpy inputs under "inputs" (pose_reference.preprocess's keyword arguments):
     every 10th (i % 10 == 3) lies behind the camera (culled), every 20th (i % 20 == 7) is a large
     Gaussian centred outside the 1.3 tan(fov) guard band whose footprint still reaches the image
     (xmul = 0).  SH coefficients are drawn for degree 3 and the DC term of any channel whose colour sum
     comes within 5e-3 of the clamp at 0 is moved away from it.  "grad2d": (P, 12) standard normal, slots
-    10 and 11 zero.  "visible": dense_reference.geometry_f32's decision."""
+    10 and 11 zero.  "visible": dense_reference.geometry_f32's decision.
+
+    edge=True (the edge scene; every extra draw is made inside this option, so the default cases are
+    unchanged) adds, by index: i % 20 == 17 the same large out-of-band Gaussians in y (ymul = 0);
+    i % 20 == 11 small Gaussians just inside the near plane (z in [0.21, 0.5], visible); i % 20 == 1
+    small ones in front of the camera but nearer than 0.2 (z in [0.02, 0.19], culled, not by tz <= 0);
+    i % 4 == 0 opacities in [0.992, 1.0], so alpha saturates at 0.99 around those centres; the behind
+    class is redrawn with z in [-5, 0].  "classes": name -> boolean row mask (EDGE_CLASSES)."""
     import numpy as np
     cam = cam or posed_camera()
     rng = np.random.default_rng(1000 + seed)
@@ -162,12 +207,28 @@ def make_case(P, D=3, colors=False, cov3D=False, seed=0, cam=None, behind=True, 
     if behind:
         back = i % 10 == 3
         z[back] = rng.uniform(-5.0, 0.1, int(back.sum()))
+    small = np.zeros(P, bool)
+    if edge:
+        n = lambda m: int(m.sum())
+        back, far_y, near_in, near_out = i % 10 == 3, i % 20 == 17, i % 20 == 11, i % 20 == 1
+        z[back] = rng.uniform(-5.0, 0.0, n(back))
+        u[far_y, 1] = rng.choice([-1.0, 1.0], n(far_y)) * rng.uniform(1.4, 1.6, n(far_y)) * cam.tanfovy
+        z[far_y] = rng.uniform(3.0, 5.0, n(far_y))
+        log_s[far_y] = np.log(rng.uniform(0.7, 1.0, (n(far_y), 3)))
+        z[near_in] = rng.uniform(0.21, 0.5, n(near_in))
+        z[near_out] = rng.uniform(0.02, 0.19, n(near_out))
+        small = near_in | near_out
+        u[small] *= 0.8
+        log_s[small] = np.log(rng.uniform(0.002, 0.01, (n(small), 3)))
     pv = np.stack([u[:, 0] * z, u[:, 1] * z, z], 1)
     means = (pv - wv[3, :3]) @ wv[:3, :3].T
     q = rng.standard_normal((P, 4))
     q /= np.linalg.norm(q, axis=1, keepdims=True)
     f32 = lambda a: np.ascontiguousarray(a, np.float32)
     inputs = dict(means=f32(means), opac=f32(rng.uniform(0.1, 0.9, P)), D=int(D))
+    if edge:
+        opaque = i % 4 == 0
+        inputs["opac"][opaque] = f32(rng.uniform(0.992, 1.0, int(opaque.sum())))
     scales, rots = f32(np.exp(log_s)), f32(q)
     if cov3D:
         r, x, y, w = (rots[:, k].astype(np.float64) for k in range(4))
@@ -195,4 +256,13 @@ def make_case(P, D=3, colors=False, cov3D=False, seed=0, cam=None, behind=True, 
     g2[:, 10:] = 0.0
     geom = geometry_f32(cam, inputs["means"], inputs["opac"], inputs.get("scales"), inputs.get("rots"),
                         inputs.get("cov3D"))
-    return dict(cam=cam, inputs=inputs, grad2d=f32(g2), visible=geom["visible"].numpy().copy(), geom=geom)
+    case = dict(cam=cam, inputs=inputs, grad2d=f32(g2), visible=geom["visible"].numpy().copy(), geom=geom)
+    if edge:
+        case["classes"] = dict(band_x=i % 20 == 7, band_y=far_y, behind=back, near_in=near_in, near_out=near_out,
+                               opaque=opaque)
+        case["classes"]["plain"] = ~np.logical_or.reduce(list(case["classes"].values()))
+    return case
+
+
+EDGE_VISIBLE = ("band_x", "band_y", "near_in", "opaque", "plain")  # the classes whose members are (mostly) visible
+EDGE_CULLED = ("behind", "near_out")                               # entirely culled
