@@ -39,6 +39,9 @@ HIP_SOURCES = {
     "gsr_tilesort.hip": [],
     # F6 and B1 must evaluate alpha / T identically; no SLP packing (it splits DPP-fused adds)
     "gsr_blend.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
+    # the score replay recomputes F6's alpha / T from the text gsr_blend.hip compiles
+    # (csrc/gsr_blend_dev.h): its flags must stay equal to that entry's
+    "gsr_scores.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
     # recomputes the forward's SH clamp bits (and r, coef under anti-aliasing) from the text
     # gsr_preprocess.hip compiles, csrc/gsr_gauss_dev.h: the bits agree because the flag is the same,
     # so these two entries must stay equal

@@ -1056,6 +1056,45 @@ int gsr_backward_preprocess(const gsr_camera* cam, const gsr_gaussians* gs, cons
     return 0;
 }
 
+// ---- importance scores ----
+size_t gsr_scores_scratch_bytes(int32_t capacity) { return ScoreLayout(capacity).total; }
+
+int gsr_forward_scores(const gsr_camera* cam, const gsr_gaussians* gs, const gsr_raster_settings* rs,
+                       const gsr_buffers* bufs, gsr_alloc_fn alloc_scratch, void* ctx, const gsr_scores* out,
+                       int32_t accumulate, void* stream_) {
+    g_err.clear();
+    if (!cam || !gs || !bufs) return fail(-1, "gsr_forward_scores: null camera / gaussians / buffers");
+    if (int e = validate(cam, gs, rs)) return e;
+    if (!out || (!out->max_w && !out->sum_w && !out->hits))
+        return fail(-1, "gsr_forward_scores: null gsr_scores / all three outputs NULL");
+    if (accumulate != 0 && accumulate != 1) return fail(-1, "gsr_forward_scores: accumulate must be 0 or 1");
+    if (!full_image(cam, rs))
+        return fail(-1, "gsr_forward_scores: full images only (tile rows [%d, %d) of %d are a band)", rs->tile_y0,
+                    rs->tile_y1, div_up(cam->height, kTile));
+    if (!alloc_scratch) return fail(-1, "gsr_forward_scores: null scratch allocator");
+    if (gs->P == 0) return 0;
+    if (bufs->n_local != gs->P)
+        return fail(-1, "gsr_forward_scores: the buffers index %d entries, not the %d Gaussians (views-mode and "
+                        "band buffers carry no scores)", bufs->n_local, gs->P);
+    if (!bufs->geom || !bufs->image || !bufs->binning) return fail(-1, "gsr_forward_scores: missing forward buffers");
+    if (int e = check_layout(cam, 0, div_up(cam->height, kTile), bufs, rs)) return e;  // before any allocation
+    hipStream_t stream = (hipStream_t)stream_;
+    const bool debug = (rs->flags & GSR_FLAG_DEBUG) != 0;
+    const long long cap = bufs->capacity;
+    const Views v = views(cam, gs->P, bufs);
+    void* scratch = alloc_scratch(ctx, ScoreLayout(cap).total);
+    if (!scratch) return fail(-2, "allocation failed (score scratch, %lld instances)", cap);
+    // only the per-entry flag bytes are zeroed: the gather reads the entries the replay flagged
+    GSR_STAGE(GSR_STAGE_MISC, launch_clear_score_flags(scratch, cap, stream), "clear score flags");
+    GSR_STAGE(GSR_STAGE_BLEND_FWD, launch_score_replay(*cam, v.ranges, v.sorted_gid, v.rect, v.rec, scratch, cap,
+                                                       v.term, v.ck, v.mk, stream),
+              "score replay");
+    GSR_STAGE(GSR_STAGE_GATHER, launch_score_gather(v.offsets, scratch, cap, gs->P, v.presort ? v.rrect : nullptr,
+                                                    out->max_w, out->sum_w, out->hits, accumulate != 0, stream),
+              "score gather");
+    return 0;
+}
+
 // ---- multi-GPU: Gaussian shards x tile-row bands ----
 int gsr_shard_forward(const gsr_camera* cam, const gsr_gaussians* gs, const gsr_raster_settings* rs, int32_t nbands,
                       const int32_t* band_rows, int32_t pair_cap, void* send, int32_t* radii, void* shard_state,

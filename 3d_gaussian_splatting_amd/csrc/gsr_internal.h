@@ -251,8 +251,23 @@ struct PartLayout {
     }
 };
 
+// Score replay output (gsr_scores.hip), one entry per (tile, instance) at emission index j like B1's:
+// 12 B -- max w, sum w, contributing pixels -- as three arrays, and the flag byte of the entries the
+// replay wrote (the only bytes cleared before it; the gather reads flagged entries only).
+struct ScoreLayout {
+    size_t mx, sm, ct, fl, total;
+    explicit ScoreLayout(long long K) {
+        const size_t n = (size_t)(K > 0 ? K : 1);
+        mx = 0;
+        sm = align_up(4 * n);
+        ct = sm + align_up(4 * n);
+        fl = ct + align_up(4 * n);
+        total = fl + align_up(n);
+    }
+};
+
 // ---- multi-GPU exchange (gsr_shard.hip) ----
-constexpr int kMaxBands = 16;       // tile-row bands (ranks) of one exchange
+constexpr int kMaxBands = 16;      // tile-row bands (ranks) of one exchange
 constexpr int kMaxHistRows = 4096;  // tile rows the per-row instance histogram covers
 constexpr int kSplatBytes = GSR_SPLAT_BYTES;
 constexpr int kSplatGradBytes = GSR_SPLAT_GRAD_BYTES;

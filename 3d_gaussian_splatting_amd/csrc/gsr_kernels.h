@@ -167,6 +167,21 @@ int launch_blend_backward(const gsr_camera& cam, const float bg[3], int ty0, int
                           const uint8_t* mk = nullptr, const B1Aux* aux = nullptr);
 // (vgy, vh: views mode -- bands of vgy tile rows per view, vh valid pixel rows each; 0 = one image)
 
+// ---- gsr_scores.hip ----
+// Importance scores of a forward's view (gsr_forward_scores; full images outside views mode).  The
+// replay walks every tile's list as F6 did (same alpha, T and termination, from F6's mk / term / ck
+// leftovers) and writes per contributing (tile, instance) its max w, sum w and pixel count at B1's
+// emission index j < cap into scratch (ScoreLayout(cap)); launch_clear_score_flags (cap flag bytes)
+// must precede it.  The gather combines each Gaussian's flagged entries in entry order -- max, +, +
+// -- into the non-null outputs (P each; zeros for culled Gaussians), replacing or, with accumulate,
+// combining with their contents.  offsets / rrect: as launch_gather_grad2d's.  No atomics.
+int launch_clear_score_flags(void* scratch, long long cap, hipStream_t s);
+int launch_score_replay(const gsr_camera& cam, const uint2* ranges, const uint32_t* sorted_gid, const uint4* rect,
+                        const float4* rec, void* scratch, long long cap, const uint32_t* term, const float4* ck,
+                        const uint8_t* mk, hipStream_t s);
+int launch_score_gather(const uint32_t* offsets, void* scratch, long long cap, int P, const uint4* rrect,
+                        float* max_w, float* sum_w, uint32_t* hits, bool accumulate, hipStream_t s);
+
 // record layout constants shared by preprocess and the blend kernels
 constexpr float kLn2 = 0.6931471805599453f;  // conic A = -2 ln2 a', B = -ln2 b', C = -2 ln2 c' 
 

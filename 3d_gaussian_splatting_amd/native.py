@@ -53,7 +53,8 @@ EXPORTS = ["gsr_abi_version", "gsr_last_error", "gsr_forward", "gsr_read_num_ren
            "gsr_image_bytes", "gsr_scratch_bytes", "gsr_ck_pool_slots", "gsr_profile_enable", "gsr_profile_read",
            "gsr_stage_name", "gsr_band_publish", "gsr_gather_finish", "gsr_forward_aux", "gsr_backward_aux",
            "gsr_binning_bytes_aux", "gsr_image_bytes_aux", "gsr_scratch_bytes_aux",
-           "gsr_camera_grad_scratch_bytes", "gsr_backward_camera", "gsr_backward_posed"]
+           "gsr_camera_grad_scratch_bytes", "gsr_backward_camera", "gsr_backward_posed",
+           "gsr_scores_scratch_bytes", "gsr_forward_scores"]
 CAMERA_GRAD_FLOATS = 36  # gsr.h GSR_CAMERA_GRAD_FLOATS: dL/dviewmatrix[16], dL/dprojmatrix[16], dL/dcampos[3], 0
 # include/gsr/gsr_train.h (training-step kernels)
 TRAIN_EXPORTS = ["gsr_activate", "gsr_loss_scratch_bytes", "gsr_loss_forward", "gsr_loss_backward", "gsr_adam_step",
@@ -111,6 +112,11 @@ class AuxOut(ctypes.Structure):
 
 class AuxGrads(ctypes.Structure):
     _fields_ = [("dL_ddepth", ctypes.c_void_p), ("dL_dalpha", ctypes.c_void_p)]
+
+
+class Scores(ctypes.Structure):
+    """gsr.h gsr_scores: per-Gaussian importance outputs (each P, device, nullable)."""
+    _fields_ = [("max_w", ctypes.c_void_p), ("sum_w", ctypes.c_void_p), ("hits", ctypes.c_void_p)]
 
 
 class AdamGroup(ctypes.Structure):
@@ -187,6 +193,12 @@ def load_hip() -> ctypes.CDLL:
         L.gsr_backward_posed.argtypes = [ctypes.POINTER(Camera), ctypes.POINTER(Gaussians), ctypes.POINTER(Settings),
                                          ctypes.POINTER(Buffers), vp, ctypes.POINTER(AuxGrads), ALLOC_FN, vp,
                                          ctypes.POINTER(Grads), vp, vp]
+        # importance scores of a forward's view: replay + per-Gaussian gather
+        L.gsr_scores_scratch_bytes.restype = ctypes.c_size_t
+        L.gsr_scores_scratch_bytes.argtypes = [i32]
+        L.gsr_forward_scores.restype = ctypes.c_int
+        L.gsr_forward_scores.argtypes = [ctypes.POINTER(Camera), ctypes.POINTER(Gaussians), ctypes.POINTER(Settings),
+                                         ctypes.POINTER(Buffers), ALLOC_FN, vp, ctypes.POINTER(Scores), i32, vp]
         # multi-GPU split: shard F1 + pack, band F2..F6, band B1, shard sum + B2
         pi32 = ctypes.POINTER(i32)
         L.gsr_exchange_block_bytes.restype = ctypes.c_size_t

@@ -21,6 +21,9 @@ from . import native
 from .graphics import RasterCamera
 
 INT32_MAX = 2**31 - 1
+# gsr.h gsr_scores, in the struct's order (hits is uint32 there; torch has no arithmetic on it)
+SCORE_NAMES = ("max_w", "sum_w", "hits")
+SCORE_DTYPES = {"max_w": torch.float32, "sum_w": torch.float32, "hits": torch.int32}
 
 
 def _ptr(t):
@@ -449,6 +452,33 @@ class CAbiRasterizer:
         self._check(rc, "gsr_backward_preprocess")
         return out
 
+    def scores(self, st: ForwardState, into: dict | None = None) -> dict:
+        """gsr_forward_scores on a forward's state (forward / forward_aux / one of forward_batch's):
+        per Gaussian, over the pixels the view blended it into with weight w = T alpha, "max_w" and
+        "sum_w" (float32 (P,)) and "hits", the number of those pixels (int32 (P,)); zeros for a
+        Gaussian the view does not use.  into: a dict of some or all of those tensors to combine the
+        view with instead (max, +, +; accumulate = 1) -- a key left out is not computed.  Returns the
+        dict written."""
+        P = st.gauss.P
+        if into is None:
+            out = {k: torch.empty(P, dtype=SCORE_DTYPES[k], device=self.device) for k in SCORE_NAMES}
+        else:
+            out = into
+            if not out or any(k not in SCORE_NAMES for k in out):
+                raise ValueError(f"scores: into must hold some of {SCORE_NAMES}, not {sorted(out)}")
+            for k, t in out.items():
+                if not (t.is_contiguous() and t.dtype == SCORE_DTYPES[k] and tuple(t.shape) == (P,)
+                        and t.device == st.color.device):
+                    raise ValueError(f"scores: into[{k!r}] must be a contiguous {SCORE_DTYPES[k]} ({P},) tensor on "
+                                     f"{st.color.device}")
+        sc = native.Scores(*[out[k].data_ptr() if k in out else None for k in SCORE_NAMES])
+        scratch = _Allocator(self.device)
+        rc = self.L.gsr_forward_scores(ctypes.byref(self._cam(st.cam)), ctypes.byref(st.gauss),
+                                       ctypes.byref(st.settings), ctypes.byref(st.buffers), scratch.cb, None,
+                                       ctypes.byref(sc), 0 if into is None else 1, self._stream())
+        self._check(rc, "gsr_forward_scores")
+        return out
+
 
 # ------------------------------------------------------------------------------------------
 # multi-GPU split (gsr_shard_* / gsr_band_*, SURVEY §8e): the compute of one rank
@@ -656,6 +686,24 @@ def apply_exposure(image, exposure, clamp=False):
     [0, 1] with `clamp`.  One fused HIP pass per direction (gsr_exposure_forward / _backward) behind
     a libtorch autograd Function, differentiable in both arguments."""
     return native.load_torch_ext().apply_exposure(image, exposure, bool(clamp))
+
+
+def gaussian_scores(cams, means3D, opacities, device=None, **inputs) -> dict:
+    """Importance of every Gaussian over `cams`: each camera is rendered (CAbiRasterizer.forward with
+    `inputs`: scales, rotations, sh_dc, ..., antialiasing, bg) and its scores accumulated in camera
+    order -- "max_w" the largest blending weight T alpha the Gaussian reaches on any pixel of any
+    view, "sum_w" its summed weight, "hits" the pixels it was blended into (CAbiRasterizer.scores).
+    No gradients.  device: the tensors' by default."""
+    cams = list(cams)
+    if not cams:
+        raise ValueError("gaussian_scores: no cameras")
+    means3D = torch.as_tensor(means3D)
+    rast = CAbiRasterizer(means3D.device if device is None else device)
+    out = None
+    with torch.no_grad():
+        for cam in cams:
+            out = rast.scores(rast.forward(cam, means3D, opacities, **inputs), into=out)
+    return out
 
 
 @dataclass

@@ -171,6 +171,7 @@ class LoopResult:
     binning_overflows: int = 0   # bounded renders whose K exceeded the bound (must stay 0)
     exact_k_reads: int = 0       # renders sized by a host read of K (after each point-set change)
     depth_loss: list = field(default_factory=list)  # (iteration, weighted loss, mean |e|, pixels) at the log points
+    importance_pruned: list = field(default_factory=list)  # (iteration, Gaussians removed) per importance pruning
 
 
 def view_sequence(n_views: int, iterations: int, seed: int = 0) -> np.ndarray:
@@ -204,6 +205,9 @@ def write_scene(path: str, scene: LoopScene, iterations: int, opt: OptimizationP
     if opt.densify_strategy != "default":
         raise ValueError("write_scene: the GSRLOOP1 file has no densification switch (the C++ loop keeps the "
                          "default clone / split / prune strategy); pass opt.densify_strategy = \"default\"")
+    if len(opt.importance_prune_iters):
+        raise ValueError("write_scene: the GSRLOOP1 file has no importance-pruning switch (the C++ loop computes no "
+                         "scores); pass opt.importance_prune_iters = ()")
     views = view_sequence(len(scene.cams), iterations, seed) if views is None else np.asarray(views, np.int32)
     H, W = int(scene.gts[0].shape[1]), int(scene.gts[0].shape[2])
     with open(path, "wb") as f:
@@ -234,7 +238,14 @@ def train(scene: LoopScene, iterations: int | None = None, opt: OptimizationPara
           progress_every: int = 0) -> LoopResult:
     """train_utils.cpp:128-145 over `scene` (GaussianTrainer.from_point_cloud = create_from_pcd,
     spatial_lr_scale = the camera extent).  progress_every > 0 prints a line to stderr every
-    that many iterations (no device sync)."""
+    that many iterations (no device sync).
+
+    opt.importance_prune_iters: after the step of each listed iteration the Gaussians whose
+    opt.importance_prune_score over ALL training cameras of the scene (the refined ones under
+    opt.train_poses) is below opt.importance_prune_threshold are dropped
+    (GaussianTrainer.prune_by_importance).  A listed iteration that also densifies is skipped: no
+    pruning happens there (the rows it would score have just been replaced).  The default empty tuple
+    runs nothing new."""
     opt = opt or OptimizationParams()
     iterations = iterations or opt.iterations
     tr = GaussianTrainer.from_point_cloud(scene.points, scene.colors, max_sh_degree, spatial_lr_scale=scene.extent,
@@ -244,6 +255,8 @@ def train(scene: LoopScene, iterations: int | None = None, opt: OptimizationPara
     if opt.train_poses:
         tr.setup_poses(len(scene.cams))
     views = view_sequence(len(scene.cams), iterations, seed)
+    prune_iters = frozenset(int(i) for i in opt.importance_prune_iters)
+    densifies = lambda it: opt.densify_from_iter < it < opt.densify_until_iter and it % opt.densification_interval == 0
     res = LoopResult(iterations=iterations, seconds=0.0, iters_per_s=0.0)
     logged, depth_logged = [], []
     torch.cuda.synchronize()
@@ -260,8 +273,12 @@ def train(scene: LoopScene, iterations: int | None = None, opt: OptimizationPara
             logged.append((it, out["stats"]))
             if "depth_stats" in out:
                 depth_logged.append((it, out["depth_stats"]))
-        if it < opt.densify_until_iter and it > opt.densify_from_iter and it % opt.densification_interval == 0:
+        if densifies(it):
             res.num_points.append((it, tr.num_points))
+        if it in prune_iters and not densifies(it):
+            cams = tr.refined_cameras(scene.cams) if opt.train_poses else scene.cams
+            res.importance_pruned.append((it, tr.prune_by_importance(cams, score=opt.importance_prune_score,
+                                                                     threshold=opt.importance_prune_threshold)))
         res.peak_points = max(res.peak_points, tr.num_points)
         if progress_every and it % progress_every == 0:
             print(f"[loop] iteration {it} points {tr.num_points} {time.perf_counter() - t0:.1f} s", file=sys.stderr,

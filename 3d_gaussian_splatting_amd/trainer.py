@@ -131,10 +131,20 @@ class OptimizationParams:
     scale_reg: float = 0.01
     mcmc_min_opacity: float = 0.005
     mcmc_growth: float = 1.05
+    # importance pruning (RadSplat's post-hoc pruning; LightGaussian and Mini-Splatting rank alike;
+    # neither upstream 3DGS nor the reference has it): at these iterations train_loop.train drops the
+    # Gaussians whose score over all training views (GaussianTrainer.importance: "max_w", "sum_w" or
+    # "hits") is below the threshold -- 0.01 on max_w is RadSplat's value.  An iteration that also
+    # densifies is skipped.  Empty: nothing new runs.  Refused with densify_strategy = "mcmc", whose
+    # cap-bound point set must not shrink
+    importance_prune_iters: tuple = ()
+    importance_prune_score: str = "max_w"
+    importance_prune_threshold: float = 0.01
 
 
 OPTIMIZER_TYPES = ("default", "sparse_adam")
 DENSIFY_STRATEGIES = ("default", "mcmc")
+IMPORTANCE_SCORES = ("max_w", "sum_w", "hits")  # rasterizer.SCORE_NAMES
 
 
 class PoseState:
@@ -651,6 +661,18 @@ class GaussianTrainer:
                 raise ValueError(f"mcmc_growth must be a finite number >= 1, not {opt.mcmc_growth!r}")
             if int(opt.cap_max) < 1:
                 raise ValueError(f"cap_max must be positive, not {opt.cap_max!r}")
+        if opt.importance_prune_score not in IMPORTANCE_SCORES:
+            raise ValueError(f"importance_prune_score must be one of {IMPORTANCE_SCORES}, not "
+                             f"{opt.importance_prune_score!r}")
+        if not (math.isfinite(opt.importance_prune_threshold) and opt.importance_prune_threshold >= 0.0):
+            raise ValueError("importance_prune_threshold must be a finite, non-negative number, not "
+                             f"{opt.importance_prune_threshold!r}")
+        if any(int(i) != i or i < 1 for i in opt.importance_prune_iters):
+            raise ValueError(f"importance_prune_iters must be positive iteration numbers, not "
+                             f"{opt.importance_prune_iters!r}")
+        if opt.densify_strategy == "mcmc" and len(opt.importance_prune_iters):
+            raise ValueError("importance_prune_iters cannot be combined with densify_strategy = \"mcmc\": its "
+                             "point set is held at cap_max and must not shrink")
         for name in ("pose_lr_init", "pose_lr_final", "pose_lr_delay_mult"):
             v = getattr(opt, name)
             if not (math.isfinite(v) and v >= 0.0):
@@ -771,18 +793,21 @@ class GaussianTrainer:
             self.active_sh_degree += 1
 
     # ---------------------------------------------------------------- one iteration
-    def render(self, cam, bg=(0.0, 0.0, 0.0), aux: bool = False):
-        """The bounded forward of one iteration; aux: gsr_forward_aux (depth and alpha planes too,
-        inverse depth per opt.depth_inverse) under the same bound and device guard."""
+    def _forward(self, cam, bg, bound: int, aux: bool = False):
+        """A forward of the current parameters under the binning bound `bound` (0: sized exactly)."""
         s, q, o = self.k.activate(self.params["scaling"], self.params["rotation"], self.params["opacity"])
         p = self.params
-        bound = self.binning.bound()
         kw = dict(scales=s, rotations=q, sh_dc=p["f_dc"], sh_rest=p["f_rest"] if p["f_rest"].shape[1] else None,
                   sh_degree=self.active_sh_degree, bg=bg, max_rendered=bound, antialiasing=self.opt.antialiasing)
         if aux:
-            st = self.rast.forward_aux(cam, p["xyz"], o.reshape(-1), inverse_depth=self.opt.depth_inverse, **kw)
-        else:
-            st = self.rast.forward(cam, p["xyz"], o.reshape(-1), **kw)
+            return self.rast.forward_aux(cam, p["xyz"], o.reshape(-1), inverse_depth=self.opt.depth_inverse, **kw)
+        return self.rast.forward(cam, p["xyz"], o.reshape(-1), **kw)
+
+    def render(self, cam, bg=(0.0, 0.0, 0.0), aux: bool = False):
+        """The bounded forward of one iteration; aux: gsr_forward_aux (depth and alpha planes too,
+        inverse depth per opt.depth_inverse) under the same bound and device guard."""
+        bound = self.binning.bound()
+        st = self._forward(cam, bg, bound, aux)
         # device-side guard of this iteration's statistics / Adam step (see BinningCapacity)
         self._guard = (st.k_device(), bound) if bound > 0 else None
         self.binning.observe(st)
@@ -1051,6 +1076,59 @@ class GaussianTrainer:
         for (a, k), t in zip(names, out):
             {"p": self.params, "m": self.exp_avg, "v": self.exp_avg_sq}[a][k] = t
         self.xyz_gradient_accum, self.denom, self.max_radii2D = out[-3], out[-2], out[-1]
+
+    # ---------------------------------------------------------------- importance pruning
+    def importance(self, cams, bg=(0.0, 0.0, 0.0)) -> dict:
+        """The Gaussians' scores over `cams`, as the trainer renders them (active SH degree,
+        opt.antialiasing): {"max_w", "sum_w" (float32 (P,)), "hits" (int32 (P,))}, accumulated in camera
+        order by gsr_forward_scores.  Each view is rendered with exact sizing (one host read of K per
+        view, no overflow: the scores are complete) and leaves the step's binning bound and device
+        guard alone.  With opt.train_poses pass refined_cameras(cams)."""
+        cams = list(cams)
+        if not cams:
+            raise ValueError("importance: no cameras")
+        out = None
+        for cam in cams:
+            out = self.rast.scores(self._forward(cam, bg, 0), into=out)
+        return out
+
+    @staticmethod
+    def _check_prune_args(score, threshold, keep_ratio):
+        if score not in IMPORTANCE_SCORES:
+            raise ValueError(f"prune_by_importance: score must be one of {IMPORTANCE_SCORES}, not {score!r}")
+        if (threshold is None) == (keep_ratio is None):
+            raise ValueError("prune_by_importance: give exactly one of threshold and keep_ratio")
+        if threshold is not None and not (math.isfinite(threshold) and threshold >= 0.0):
+            raise ValueError(f"prune_by_importance: threshold must be a finite, non-negative number, not {threshold!r}")
+        if keep_ratio is not None and not 0.0 < keep_ratio <= 1.0:
+            raise ValueError(f"prune_by_importance: keep_ratio must lie in (0, 1], not {keep_ratio!r}")
+
+    def prune_by_importance(self, cams, score: str = "max_w", threshold: float | None = None,
+                            keep_ratio: float | None = None, bg=(0.0, 0.0, 0.0)) -> int:
+        """Drop the Gaussians the views `cams` use least, by importance(cams)[score]: with `threshold`
+        those whose score is below it (RadSplat: max_w < 0.01); with `keep_ratio` all but the
+        ceil(keep_ratio P) highest-scoring ones, ties broken by index (the lower index stays).  Exactly
+        one of the two.  The rows go through prune_points, so the Adam moments and the densification
+        statistics stay aligned, and the next render is sized exactly.  Refused under
+        densify_strategy = "mcmc" (the point set is held at cap_max).  Returns the number removed."""
+        self._check_prune_args(score, threshold, keep_ratio)
+        if self.opt.densify_strategy == "mcmc":
+            raise ValueError("prune_by_importance: densify_strategy = \"mcmc\" holds the point set at cap_max; "
+                             "it must not shrink")
+        s = self.importance(cams, bg)[score]
+        P = self.num_points
+        if threshold is not None:
+            mask = s < threshold
+        else:
+            keep = min(P, math.ceil(keep_ratio * P - 1e-9))
+            order = torch.sort(s, descending=True, stable=True).indices
+            mask = torch.ones(P, dtype=torch.bool, device=self.device)
+            mask[order[:keep]] = False
+        removed = int(mask.sum().item())
+        if removed:
+            self.prune_points(mask)
+            self.binning.reset()
+        return removed
 
     def _rows(self, mask: torch.Tensor) -> dict:
         idx = self.k.compact_index(mask)

@@ -319,6 +319,50 @@ int gsr_backward_posed(const gsr_camera* cam, const gsr_gaussians* gs, const gsr
                        gsr_alloc_fn alloc_scratch, void* alloc_ctx, const gsr_grads* grads, float* dL_dcamera,
                        void* stream);
 
+/* ---- Importance scores ----
+ * Which Gaussians a rendered view actually uses: per Gaussian, three moments of its blending weight
+ * w = T_i alpha_i over the pixels it was blended into -- exactly the (pixel, Gaussian) pairs the
+ * forward blended (same alpha >= 1/255 and power > 0 rejections, same T < 1e-4 termination: the
+ * kernel replays the forward's list with the forward's own instructions), pixels outside the image
+ * never counted:
+ *   max_w[g] = max over pixels of w     sum_w[g] = sum over pixels of w     hits[g] = number of pixels
+ * A culled Gaussian (radii == 0), one hidden behind opaque ones, or one that never reaches
+ * alpha >= 1/255 gets 0, 0, 0.  Post-training compression ranks by these (max_w < 0.01 is RadSplat's
+ * pruning test; sum_w and hits are LightGaussian's / Mini-Splatting's).
+ *
+ * bufs: a forward's, unchanged -- gsr_forward's, gsr_forward_aux's or one view's of gsr_forward_batch --
+ * with that forward's cam, gs and rs.  The call reads the buffers only (a backward may follow or
+ * precede it) and launches three stages: a clear of capacity flag bytes, the replay (one entry of
+ * 12 B per contributing (tile, Gaussian) instance, at the emission index the backward uses; booked
+ * under GSR_STAGE_BLEND_FWD) and a per-Gaussian gather in fixed entry order (GSR_STAGE_GATHER).  No
+ * float atomics: two calls give the same bits.  alloc_scratch is asked once, for
+ * gsr_scores_scratch_bytes(bufs->capacity) (the 12-B entries and their flag bytes).
+ *
+ * out: each array P, device, nullable, at least one non-NULL; a NULL array is skipped.
+ * accumulate == 0 writes the arrays; accumulate == 1 combines with what they hold -- max for max_w,
+ * + for sum_w and hits -- so a loop over views needs no kernel of the caller's, and its result is
+ * fixed by the call order: ((s_0 + s_1) + s_2) ...
+ * Under GSR_FLAG_ANTIALIAS the scores are those of o' (the records carry it); the flag must agree with
+ * the layout word, as for every backward.
+ * Refused (< 0, gsr_last_error) before any allocation or launch: null cam / gs / bufs; out NULL or all
+ * three arrays NULL; a tile band in rs; buffers that do not index gs->P entries (views-mode buffers of
+ * gsr_forward_views, band buffers); a layout word without the tag or one that disagrees with the
+ * buffers (GSR_ERR_LAYOUT); an anti-alias flag that disagrees with the layout (GSR_ERR_LAYOUT).
+ * Under a binning bound that overflowed (rs->max_rendered < K) the call stays inside its buffers and
+ * returns 0; the scores are then incomplete, which the caller learns from gsr_read_num_rendered, as
+ * for the image.
+ * Not covered: gsr_forward_views' buffers and the multi-GPU calls (gsr_shard_*, gsr_band_*) give no
+ * scores. */
+typedef struct gsr_scores {      /* each P, device, nullable; at least one non-NULL */
+    float*    max_w;             /* max over pixels of T_i alpha_i                   */
+    float*    sum_w;             /* sum over pixels of T_i alpha_i                   */
+    uint32_t* hits;              /* pixels the Gaussian was blended into             */
+} gsr_scores;
+size_t gsr_scores_scratch_bytes(int32_t capacity);
+int gsr_forward_scores(const gsr_camera* cam, const gsr_gaussians* gs, const gsr_raster_settings* rs,
+                       const gsr_buffers* bufs, gsr_alloc_fn alloc_scratch, void* alloc_ctx,
+                       const gsr_scores* out, int32_t accumulate, void* stream);
+
 /* ---- Multi-GPU: Gaussian shards x tile-row bands (the scaling version) ----
  * Rank r of N owns the Gaussian shard [g0_r, g1_r) (contiguous, in rank order) and the band
  * of tile rows [band_rows[r], band_rows[r+1]).  One step:
