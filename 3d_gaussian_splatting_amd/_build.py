@@ -12,7 +12,8 @@ Per-file flags: gsr_preprocess.hip is compiled with -ffp-contract=off so its key
 arithmetic is bit-identical to the CPU oracle; the blend and preprocess-backward files too
 (B1 replays the forward's alpha / T bit for bit; B2 recomputes clamp bits from the text F1
 compiles, csrc/gsr_gauss_dev.h, which needs the two files' flags equal); the
-training kernels keep hipcc's default FMA contraction (compared within tolerance).
+training kernels (gsr_loss.hip, gsr_optim.hip, gsr_pointset.hip) keep hipcc's default FMA
+contraction (compared within tolerance).
 """
 from __future__ import annotations
 
@@ -49,8 +50,12 @@ HIP_SOURCES = {
     # camera gradients: the same header under default flags -- it reads the stored clamp bits
     # (recomputes none) and is tolerance-compared
     "gsr_camera_bwd.hip": [],
-    # training-step kernels (loss, fused Adam, densification): tolerance-compared, default flags
-    "gsr_train.hip": [],
+    # training-step kernels, sharing csrc/gsr_train_dev.h: the image-plane losses, the per-iteration
+    # work on the Gaussian arrays (activations, fused Adam, statistics, MCMC noise), the point-set
+    # edits (compaction, gather, relocation); tolerance-compared, default flags
+    "gsr_loss.hip": [],
+    "gsr_optim.hip": [],
+    "gsr_pointset.hip": [],
     # point-cloud initialisation (exact k-NN): box and point distances must round alike
     "gsr_init.hip": ["-ffp-contract=off"],
     # multi-GPU splat pack / unpack / gradient sum (copies and integer work)

@@ -660,7 +660,7 @@ int views_camera(int32_t V, const gsr_camera* cams, const gsr_gaussians* gs, con
 }  // namespace
 
 namespace gsr {
-// error hook for the other translation units of the library (gsr_train.hip)
+// error hook for the other translation units of the library (declared in gsr_internal.h)
 int set_error(int code, const char* msg) {
     g_err = msg;
     return code;

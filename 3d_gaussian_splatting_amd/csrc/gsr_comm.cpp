@@ -9,10 +9,7 @@
 #include <string>
 
 #include "gsr/gsr_comm.h"
-
-namespace gsr {
-int set_error(int code, const char* msg);  // gsr_api.cpp: the thread-local gsr_last_error text
-}
+#include "gsr_internal.h"  // set_error: the thread-local gsr_last_error text
 
 static_assert(GSR_COMM_ID_BYTES == sizeof(ncclUniqueId), "ncclUniqueId size");
 

@@ -20,11 +20,9 @@
 #include <cfloat>
 
 #include "gsr_kernels.h"
-#include "../../include/gsr/gsr_train.h"
+#include "gsr/gsr_train.h"
 
 namespace gsr {
-int set_error(int code, const char* msg);
-
 namespace {
 
 constexpr int kBox = 256;  // sorted points per box (= threads per box block)

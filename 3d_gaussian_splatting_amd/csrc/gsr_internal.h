@@ -16,6 +16,9 @@
 
 namespace gsr {
 
+// defined in gsr_api.cpp: sets the thread-local error text read by gsr_last_error()
+int set_error(int code, const char* msg);
+
 constexpr int kTile = GSR_TILE;
 constexpr int kSortBlock = 256;             // threads per radix-sort / scan block
 constexpr int kSortItems = 16;              // items per thread

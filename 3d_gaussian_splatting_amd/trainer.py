@@ -213,6 +213,17 @@ class TrainKernels:
         if rc != 0:
             raise RuntimeError(f"{what} failed ({rc}): {native.last_error()}")
 
+    def _need(self, what, name, t, shape, dtype=torch.float32):
+        """t must be contiguous, of `dtype`, on this device and, unless `shape` is None, of that
+        shape; a str entry of `shape` ("P") stands for any size."""
+        ok = t.is_contiguous() and t.dtype == dtype and t.device == self.device
+        if ok and shape is not None and tuple(t.shape) != shape:
+            ok = t.dim() == len(shape) and all(isinstance(s, str) or int(d) == s for d, s in zip(t.shape, shape))
+        if not ok:
+            txt = "" if shape is None else "(" + ", ".join(map(str, shape)) + ("," if len(shape) == 1 else "") + ") "
+            raise ValueError(f"{what}: {name} must be a contiguous {'f32' if dtype == torch.float32 else 'int32'} "
+                             f"{txt}tensor on {self.device}")
+
     def activate(self, scale_raw, rot_raw, opac_raw):
         P = int(scale_raw.shape[0])
         s = torch.empty_like(scale_raw)
@@ -248,13 +259,9 @@ class TrainKernels:
         dL/dloss = 1.  Planes may be any f32 views with contiguous pixels (a 1-element offset takes
         the kernel's scalar path)."""
         H, W = (int(v) for v in depth.shape)
-        planes = dict(depth=depth, target=target, mask=mask, alpha=alpha)
-        for name, t in planes.items():
-            if t is None:
-                continue
-            if not (t.is_contiguous() and t.dtype == torch.float32 and t.device == self.device
-                    and tuple(t.shape) == (H, W)):
-                raise ValueError(f"depth_loss: {name} must be a contiguous f32 ({H}, {W}) tensor on {self.device}")
+        for name, t in dict(depth=depth, target=target, mask=mask, alpha=alpha).items():
+            if t is not None:
+                self._need("depth_loss", name, t, (H, W))
         if normalized and alpha is None:
             raise ValueError("depth_loss: normalized mode needs alpha")
         scratch = torch.empty(int(self.L.gsr_depth_loss_scratch_bytes(H, W)), dtype=torch.uint8, device=self.device)
@@ -273,14 +280,9 @@ class TrainKernels:
             raise ValueError(f"{what}: img must be (3, H, W)")
         H, W = int(img.shape[1]), int(img.shape[2])
         for name, t in (("img", img), ("dL_dout", extra)):
-            if t is None:
-                continue
-            if not (t.is_contiguous() and t.dtype == torch.float32 and t.device == self.device
-                    and tuple(t.shape) == (3, H, W)):
-                raise ValueError(f"{what}: {name} must be a contiguous f32 (3, {H}, {W}) tensor on {self.device}")
-        if not (exposure.is_contiguous() and exposure.dtype == torch.float32 and exposure.device == self.device
-                and tuple(exposure.shape) == (3, 4)):
-            raise ValueError(f"{what}: exposure must be a contiguous f32 (3, 4) tensor on {self.device}")
+            if t is not None:
+                self._need(what, name, t, (3, H, W))
+        self._need(what, "exposure", exposure, (3, 4))
         return H, W
 
     def exposure_forward(self, img, exposure, clamp=False):
@@ -299,9 +301,7 @@ class TrainKernels:
         view (a row of a larger gradient tensor) that receives dL_dexposure instead of a new one."""
         H, W = self._exposure_args("exposure_backward", img, exposure, dL_dout)
         dE = torch.empty((3, 4), dtype=torch.float32, device=self.device) if out is None else out
-        if not (dE.is_contiguous() and dE.dtype == torch.float32 and dE.device == self.device
-                and tuple(dE.shape) == (3, 4)):
-            raise ValueError(f"exposure_backward: out must be a contiguous f32 (3, 4) tensor on {self.device}")
+        self._need("exposure_backward", "out", dE, (3, 4))
         scratch = torch.empty(int(self.L.gsr_exposure_scratch_bytes(H, W)), dtype=torch.uint8, device=self.device)
         dimg = torch.empty_like(img)
         self._check(self.L.gsr_exposure_backward(_p(img), _p(exposure), _p(dL_dout), H, W,
@@ -316,9 +316,7 @@ class TrainKernels:
         visibility: the rasterizer's radii, a contiguous int32 (P,) device tensor; only the rows of
         Gaussians with radii > 0 are stepped, the others keep their bytes (gsr_adam_step_sparse)."""
         if visibility is not None:
-            if not (visibility.is_contiguous() and visibility.dtype == torch.int32 and visibility.dim() == 1
-                    and visibility.device == self.device):
-                raise ValueError(f"adam: visibility must be a contiguous int32 (P,) tensor on {self.device}")
+            self._need("adam", "visibility", visibility, ("P",), torch.int32)
             P = int(visibility.numel())
             for g in groups:
                 n = g["param"].numel()
@@ -328,8 +326,7 @@ class TrainKernels:
         for i, g in enumerate(groups):
             for k in ("param", "grad", "exp_avg", "exp_avg_sq"):
                 t = g[k]
-                if not (t.is_contiguous() and t.dtype == torch.float32 and t.device == self.device):
-                    raise ValueError(f"adam: {k} must be a contiguous f32 tensor on {self.device}")
+                self._need("adam", k, t, None)
                 if t.numel() != g["param"].numel():
                     raise ValueError(f"adam: {k} size mismatch")
                 setattr(arr[i], k, t.data_ptr())
@@ -352,21 +349,16 @@ class TrainKernels:
         self._check(self.L.gsr_densify_stats_guarded(_p(radii), _p(dmeans2D), P, _p(max_radii2D), _p(grad_accum),
                                                      _p(denom), gk, gcap, _stream(self.device)), "gsr_densify_stats")
 
-    def _f32_rows(self, what, name, t, shape):
-        if not (t.is_contiguous() and t.dtype == torch.float32 and t.device == self.device
-                and tuple(t.shape) == tuple(shape)):
-            raise ValueError(f"{what}: {name} must be a contiguous f32 {tuple(shape)} tensor on {self.device}")
-
     def mcmc_noise(self, xyz, scale_raw, rot_raw, opac_raw, noise, strength, guard=None):
         """gsr_mcmc_noise, in place on xyz (P, 3): xyz += R diag(s^2) R^T (noise * gate * strength) from
         the raw leaves scale_raw (P, 3), rot_raw (P, 4), opac_raw (P, 1) or (P,), with noise (P, 3)
         standard-normal floats the caller drew.  guard as adam_step."""
         P = int(xyz.shape[0])
-        self._f32_rows("mcmc_noise", "xyz", xyz, (P, 3))
-        self._f32_rows("mcmc_noise", "scale_raw", scale_raw, (P, 3))
-        self._f32_rows("mcmc_noise", "rot_raw", rot_raw, (P, 4))
-        self._f32_rows("mcmc_noise", "opac_raw", opac_raw, (P, 1) if opac_raw.dim() == 2 else (P,))
-        self._f32_rows("mcmc_noise", "noise", noise, (P, 3))
+        self._need("mcmc_noise", "xyz", xyz, (P, 3))
+        self._need("mcmc_noise", "scale_raw", scale_raw, (P, 3))
+        self._need("mcmc_noise", "rot_raw", rot_raw, (P, 4))
+        self._need("mcmc_noise", "opac_raw", opac_raw, (P, 1) if opac_raw.dim() == 2 else (P,))
+        self._need("mcmc_noise", "noise", noise, (P, 3))
         gk, gcap = _guard(guard)
         self._check(self.L.gsr_mcmc_noise(_p(xyz), _p(scale_raw), _p(rot_raw), _p(opac_raw), _p(noise), P,
                                           float(strength), gk, gcap, _stream(self.device)), "gsr_mcmc_noise")
@@ -376,11 +368,9 @@ class TrainKernels:
         ratios (n,) (how many Gaussians share the row, clamped to [1, native.MCMC_MAX_RATIO]) ->
         (new_opacities (n,), new_scales (n, 3))."""
         n = int(opacities.shape[0])
-        self._f32_rows("mcmc_relocate", "opacities", opacities, (n,))
-        self._f32_rows("mcmc_relocate", "scales", scales, (n, 3))
-        if not (ratios.is_contiguous() and ratios.dtype == torch.int32 and ratios.device == self.device
-                and tuple(ratios.shape) == (n,)):
-            raise ValueError(f"mcmc_relocate: ratios must be a contiguous int32 ({n},) tensor on {self.device}")
+        self._need("mcmc_relocate", "opacities", opacities, (n,))
+        self._need("mcmc_relocate", "scales", scales, (n, 3))
+        self._need("mcmc_relocate", "ratios", ratios, (n,), torch.int32)
         new_o, new_s = torch.empty_like(opacities), torch.empty_like(scales)
         self._check(self.L.gsr_mcmc_relocate(_p(opacities), _p(scales), _p(ratios), n, float(min_opacity), _p(new_o),
                                              _p(new_s), _stream(self.device)), "gsr_mcmc_relocate")
@@ -399,8 +389,7 @@ class TrainKernels:
 
     def knn_mean_dist2(self, points: torch.Tensor) -> torch.Tensor:
         """Mean squared distance of each point to its 3 nearest others (exact; gsr_knn_mean_dist2)."""
-        if not (points.is_contiguous() and points.dtype == torch.float32 and points.device == self.device):
-            raise ValueError(f"knn: points must be a contiguous f32 (N, 3) tensor on {self.device}")
+        self._need("knn", "points", points, ("N", 3))
         n = int(points.shape[0])
         out = torch.empty(n, dtype=torch.float32, device=self.device)
         if n == 0:

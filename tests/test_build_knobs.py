@@ -57,6 +57,12 @@ def test_knob_defaults_match_design():
     assert source_knobs() == design_knobs()
 
 
+def test_build_lists_every_kernel_source():
+    """build_hip compiles the HIP_SOURCES dict, build_variant whatever csrc/ holds: the same files."""
+    on_disk = {f for f in os.listdir(CSRC) if f.endswith(".hip") or f in ("gsr_api.cpp", "gsr_comm.cpp")}
+    assert on_disk == set(pkg("_build").HIP_SOURCES)
+
+
 def test_build_passes_no_knob():
     b = pkg("_build")
     flags = list(b.COMMON) + [f for fl in b.HIP_SOURCES.values() for f in fl]
